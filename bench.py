@@ -4,6 +4,14 @@ NC-Net (5,5,5 / 16,16,1) at 400x400, bf16, synthetic pairs, random init
 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--impl hip|reference]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the record.
+``--full`` also measures the secondary records of a 1-GPU run (InLoc
+inference configs, other training sizes / recipes / precisions) into
+``config.secondary``.  ``--dump-outputs DIR`` writes what the last timed step
+returned and updated (loss, trainable parameters, their gradients) as
+``DIR/<name>.npy``.
 
 One process per GPU (torchrun env for N > 1; RCCL all-reduce of gradients).
 A step is exactly what train.py does per batch: zero_grad, backbone on the
@@ -244,6 +252,35 @@ def _fe_finetune_secondary(batch: int, size: int, steps: int = 5, warmup: int = 
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def _dump_outputs(dirname: str, loss, named_params) -> dict:
+    """--dump-outputs: what a caller of the timed step holds after the last
+    timed step -- the returned loss, and the trainable parameters (updated in
+    place by the optimizer) with the gradients the step left on them -- as
+    float32 ``<name>.npy`` files.  Above DUMP_BUDGET_BYTES in all, every array
+    is cut to the same fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    arrays = {"loss": loss.detach().float().cpu().numpy()}
+    for name, p in named_params:
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES / total
+        for name, a in arrays.items():
+            n = max(1, int(a.size * keep))
+            if n < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": dirname, "arrays": len(arrays), "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
 def _free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -304,9 +341,17 @@ def main(argv=None):
                     help="Adam learning rate (train.py's 5e-4).  Diagnostics only: the kernels' clocks depend on the "
                          "data, which drifts with the weights, so same-box kernel A/Bs whose numerics differ in the "
                          "last bits compare at --lr 0 (identical weights every step, the optimizer still runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps of a 1-GPU run, also measure the secondary records (InLoc inference "
+                         "configs, fe_finetune, nc_precision fp32 / mixed, other image sizes, the IVD recipe, batch "
+                         "16) into config.secondary; a plain run only times the headline steps")
     ap.add_argument("--inloc", type=int, default=1,
-                    help="1: after the timed training steps of a 1-GPU run, also time the InLoc inference configs "
-                         "(BASELINE configs 3-5: 1600 px bf16, 3200 px bf16, 3200 px fp8) into config.secondary")
+                    help="with --full: 0 skips every secondary record (1: the InLoc inference configs, BASELINE "
+                         "configs 3-5: 1600 px bf16, 3200 px bf16, 3200 px fp8, and the training secondaries)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write the last step's loss and the trainable parameters and their "
+                         "gradients as DIR/<name>.npy (float32; the inputs are seeded, so two builds compare "
+                         "output for output)")
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _self_launch(args, argv)
@@ -418,7 +463,12 @@ def main(argv=None):
     # the secondary records are single-GPU measurements: taken in the 1-GPU run
     # only, so the multi-GPU scaling runs stay short and rank 0 never works on
     # alone while its peers tear the process group down
-    if args.inloc and ctx.world_size == 1 and dev.type == "cuda" and args.impl == "hip":
+    dumped = None
+    if args.dump_outputs and ctx.is_main:
+        stepped = {id(p) for p in params}      # the optimizer's parameters: what a step updates
+        dumped = _dump_outputs(args.dump_outputs, loss, [(n, p) for n, p in model.named_parameters()
+                                                         if id(p) in stepped])
+    if args.full and args.inloc and ctx.world_size == 1 and dev.type == "cuda" and args.impl == "hip":
         secondary = _inloc_secondary()
         try:
             secondary["fe_finetune_1"] = _fe_finetune_secondary(SECONDARY_BATCH, s)
@@ -474,6 +524,7 @@ def main(argv=None):
                        "hbm_peak_gb": (round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 2)
                                        if dev.type == "cuda" else None),
                        "runtime": _config.RUNTIME.as_dict(),
+                       "full": bool(args.full), "dumped_outputs": dumped,
                        "secondary": secondary},
         }
         print(json.dumps(rec), flush=True)

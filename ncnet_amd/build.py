@@ -121,8 +121,11 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, v
     if variant == "debug":
         hip_flags = [f for f in hip_flags if f != "-O3"] + ["-O1", "-g", "-DNCNET_DEBUG=1"]
     elif variant == "asan":
-        hip_flags = [f for f in hip_flags if f != "-O3"] + ["-O1", "-g", "-Xarch_host", "-fsanitize=address",
-                                                             "-Xarch_host", "-fno-omit-frame-pointer"]
+        # only the host side is sanitized and built -O1 -g; the device code keeps
+        # the release flags (the inline-asm LDS-DMA of csrc/common.h needs the
+        # optimizer to keep its LDS address in a scalar register)
+        hip_flags += ["-Xarch_host", "-O1", "-Xarch_host", "-g", "-Xarch_host", "-fsanitize=address",
+                      "-Xarch_host", "-fno-omit-frame-pointer"]
 
     steps = []
     objs = []

@@ -398,7 +398,7 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
 // through a ring of KS rows x (KS + 1) column slots (each X1 plane is DMA'd by
 // the KS rows i that use it: L2 traffic on 50 MB).  Wave w accumulates taps
 // 13 (w & 1) .. +12 over the q chunks w >> 1, +4, ...; the 4 chunk-waves of a
-// tap half are reduced through LDS atomics at the end into one partial per
+// tap half are added in LDS at the end, in a fixed order, into one partial per
 // workgroup [G][NT][32 combos][16] (+ the bias sum of D on the ones-row MFMA).
 // Reference: the autograd of lib/conv4d.py:11-51 for the first / last
 // NeighConsensus layers (lib/model.py:130-139).
@@ -557,17 +557,28 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
     // ---- reduce the 4 chunk-waves of each tap half, one partial per workgroup ----
     for (int o = threadIdx.x; o < NT * 512 + 16; o += 512) red[o] = 0.f;
     __syncthreads();
-    xstatic_for<0, C::NTW>([&](auto tc) {
-      constexpr int tt = decltype(tc)::value;
-      constexpr int tap = C::NTW * TH + tt;
-      if constexpr (tap < NT) {
+    // the chunk-waves add in turn (0, 1, 2, 3), so the fp32 sum has one fixed
+    // order and the gradient is bitwise reproducible; the two tap halves write
+    // disjoint rows.  Every wave passes the same four barriers.
+    constexpr int CQ = decltype(cqc)::value;
 #pragma unroll
-        for (int grp = 0; grp < 2; ++grp)
+    for (int turn = 0; turn < 4; ++turn) {
+      if (turn == CQ) {
+        xstatic_for<0, C::NTW>([&](auto tc) {
+          constexpr int tt = decltype(tc)::value;
+          constexpr int tap = C::NTW * TH + tt;
+          if constexpr (tap < NT) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            atomicAdd(&red[(tap * 32 + 16 * grp + 4 * kg + r) * 16 + li], acc[tt][grp][r]);
+            for (int grp = 0; grp < 2; ++grp)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                red[(tap * 32 + 16 * grp + 4 * kg + r) * 16 + li] += acc[tt][grp][r];
+          }
+        });
+        if (BIAS && TH == 0 && lane < 16) red[NT * 512 + lane] += accb[0];
       }
-    });
+      __syncthreads();
+    }
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -583,8 +594,6 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
     case 6: run(I0{}, I3{}); break;
     default: run(I1{}, I3{}); break;
   }
-  if (BIAS && th == 0 && lane < 16) atomicAdd(&red[NT * 512 + lane], accb[0]);
-  __syncthreads();
   for (int o = threadIdx.x; o < NT * 512; o += 512) part[(size_t)bid * NT * 512 + o] = red[o];
   if (BIAS && threadIdx.x < 16) partb[(size_t)bid * 16 + threadIdx.x] = red[NT * 512 + threadIdx.x];
 #endif

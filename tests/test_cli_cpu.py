@@ -119,11 +119,10 @@ def test_inloc_localize_parallel_cached(workdir):
 
 
 def test_reference_refposes_parse():
-    """The reference's own GT pose file (MATLAB v5, read with scipy.io.loadmat)."""
+    """The reference's own GT pose file (MATLAB v5, read with scipy.io.loadmat),
+    stored as a test vector in tests/golden/."""
     import inloc_localize
-    path = "/root/reference/lib_matlab/DUC_refposes_all.mat"
-    if not os.path.exists(path):
-        pytest.skip("reference GT poses not present")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "DUC_refposes_all.mat")
     refs = inloc_localize.load_refposes(path)
     assert len(refs) == 198 + 131
     assert refs[0]["P"].shape == (3, 4) and refs[0]["floor"] == "DUC1"

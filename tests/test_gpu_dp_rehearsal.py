@@ -35,7 +35,20 @@ def _batch(seed, b=2, size=400):
             "target_image": torch.randn(b, 3, size, size, generator=g)}
 
 
+def _private_miopen_state(out_dir, tag):
+    """Every process of this test starts from its own empty MIOpen user
+    database and kernel cache: what the user's home holds (find results left by
+    earlier runs, or by the process that ran just before) decides which solver
+    the stem convolution gets, and the comparison below needs the same one in
+    the ranks and in the reference.  Set before the process's first convolution."""
+    for var, sub in (("MIOPEN_USER_DB_PATH", "db"), ("MIOPEN_CUSTOM_CACHE_DIR", "cache")):
+        d = os.path.join(out_dir, f"miopen_{tag}", sub)
+        os.makedirs(d, exist_ok=True)
+        os.environ[var] = d
+
+
 def _worker(rank, world, port, out_dir, steps):
+    _private_miopen_state(out_dir, f"r{rank}")
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port), NCNET_DIST_BACKEND="gloo")
     import dataclasses
@@ -73,6 +86,7 @@ def _reference_worker(_, world, out_dir, steps):
     it) -- in a fresh process like the ranks, so no state left by earlier
     tests in the pytest process (MIOpen solver caches, runtime knobs) enters
     the comparison."""
+    _private_miopen_state(out_dir, "ref")
     import dataclasses
     from ncnet_amd import config
     config.set_runtime(dataclasses.replace(config.RuntimeConfig.from_env(), trunk_conv="native"))
