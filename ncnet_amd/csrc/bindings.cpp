@@ -130,7 +130,7 @@ void pad_planes(Tensor x, Tensor y, int64_t I2, int64_t J2, int64_t ks, int64_t 
 
 // 1 -> 16 Conv4d on padded 1-channel planes Xp [V*I*J, PPL] with A fragments Wa
 // [ks^2, 64, 8]; Y bf16 [V,I,J,K,L,16]; epi 1 (bias + ReLU) or 2 (ReLU mask M).
-// Raises for shapes without an instantiation (ops/neigh_consensus.py fast1x_ok
+// Raises for shapes without an instantiation (ops/nc/train.py fast1x_ok
 // must never route one here: the outputs are uninitialised buffers).
 bool conv1x16(Tensor Xp, Tensor Wa, c10::optional<Tensor> bias, c10::optional<Tensor> M, Tensor Y, int64_t ks,
               int64_t epi) {

@@ -260,7 +260,7 @@ class ImMatchNet(nn.Module):
         # bf16 MFMA kernels), the reference's evaluation precision -- inference only
         self.corr_dtype = corr_dtype
         # nc_precision='fp32': NeighConsensus forward AND backward as bf16x3 splits
-        # (fp32-accurate training at 3x the NC cost; ops/neigh_consensus.py NeighConsensusX3Fn)
+        # (fp32-accurate training at 3x the NC cost; ops/nc/x3.py NeighConsensusX3Fn)
         # nc_precision='mixed': the cheapest mix the per-stage ablation found to
         # train like 'fp32' (profiles/r5/ablation): fp32-accurate (bf16x3) trunk
         # and NeighConsensus forward, bf16 correlation and NeighConsensus backward

@@ -9,10 +9,10 @@ on ``nn.Module`` directly -- the reference's ``_ConvNd`` subclass no longer
 constructs on modern torch.
 
 On GPU the op runs the HIP implicit-GEMM kernels (forward, data gradient,
-weight gradient) through ``neigh_consensus.conv_layer`` -- the same
+weight gradient) through ``nc/layers.py conv_layer`` -- the same
 channel-blocked / ij-encoded layer path as the NC stack, so any channel
-counts work; in the NC-Net model the fused stack in ``neigh_consensus.py``
-is used instead of per-layer calls.
+counts work; in the NC-Net model the stacks behind ``neigh_consensus.py``
+are used instead of per-layer calls.
 """
 from __future__ import annotations
 
@@ -23,8 +23,8 @@ import torch.nn as nn
 
 from . import _ext
 from . import reference as ref
-from .neigh_consensus import HIP_KS, _layer_wgrad, blocks_to_ncl, conv_layer, planar_to_blocks
-from .packing import ij_groups, transpose_for_dgrad
+from .nc.layers import HIP_KS, conv_layer, ijpack, layer_wgrad, planar_to_blocks
+from .packing import transpose_for_dgrad
 
 
 def _kind(cin: int, cout: int) -> str:
@@ -72,15 +72,9 @@ class Conv4dFn(torch.autograd.Function):
             gx = _from_out(conv_layer(gr, transpose_for_dgrad(w_std), cout, cin, relu=False, f32=True), cin).to(dt)
         if ctx.needs_input_grad[1]:
             kind = _kind(cin, cout)
-            xin = h
-            if cin == 1:
-                xin = torch.empty((ij_groups(ks),) + tuple(h.shape) + (16,), dtype=torch.bfloat16, device=h.device)
-                C.ijpack(h, xin, ks, 1)
-            gs = None
-            if kind == "1out":
-                gs = torch.empty((ij_groups(ks),) + tuple(gr.shape) + (16,), dtype=torch.bfloat16, device=h.device)
-                C.ijpack(gr, gs, ks, -1)
-            dw, _ = _layer_wgrad(C, kind, xin, gr, gs, ks, cin, cout)
+            xin = ijpack(C, h, ks, 1) if cin == 1 else h
+            gs = ijpack(C, gr, ks, -1) if kind == "1out" else None
+            dw, _ = layer_wgrad(C, kind, xin, gr, gs, ks, cin, cout)
             gw = ref.conv4d_weight_from_std(dw).to(w_ref.dtype)
         if has_bias and ctx.needs_input_grad[2]:
             gb = g.float().sum(dim=(0, 2, 3, 4, 5))

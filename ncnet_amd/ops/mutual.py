@@ -71,7 +71,7 @@ def mutual_matching_padded(corr4d: torch.Tensor, ks: int):
     """MutualMatching (autograd) that also writes its output as the zero-padded
     bf16 planes of both symmetric NeighConsensus branches for a first layer of
     kernel size ``ks`` (the training stack's conv1x16 / wgrad1x16 operand,
-    ops/neigh_consensus.py fast1x path) -> (x [V,1,I,J,K,L] fp32, planes
+    ops/nc/train.py fast1x path) -> (x [V,1,I,J,K,L] fp32, planes
     [2 V I J, PPL] bf16).  Square volumes only."""
     V, ch, I, J, K, L = corr4d.shape
     assert ch == 1 and (I, J) == (K, L)

@@ -33,1706 +33,51 @@ kernels (even kernel sizes) raises unless config.RUNTIME.allow_torch_fallback
 
 Execution paths: ``select_path`` is the ONE place that picks them (the model's
 ``process_correlation`` asks it too); ``neigh_consensus`` dispatches on its
-answer and ``_ext.DISPATCH`` counts what ran.
+answer and ``_ext.DISPATCH`` counts what ran.  This module holds only the
+selector, the dispatcher and re-exports; the paths live in ``ops/nc/``, one
+module per row group, all on the single-layer primitive ``nc/layers.py``.
 
 | path | when | implementation | tests |
 |---|---|---|---|
 | ``reference`` | CPU tensors | ``ops/reference.py`` (fp32 oracle) | ``test_nc_general_cpu.py`` |
 | ``torch_fallback`` | GPU, no HIP kernels (even kernel size) | the oracle, only with allow_torch_fallback | ``test_gpu_kernels.py`` |
-| ``x3_inference`` | precision fp32 / mixed, no autograd | ``neigh_consensus_x3`` (bf16x3 splits) | ``test_gpu_x3.py`` |
-| ``mixed`` | precision mixed, autograd, fast-path shapes | ``NeighConsensusMixedFn`` (x3 forward, bf16 backward) | ``test_gpu_x3.py`` |
-| ``x3_fused`` / ``x3`` | precision fp32 (or mixed off the fast shapes), autograd | ``NeighConsensusX3FusedFn`` / ``NeighConsensusX3Fn`` | ``test_gpu_x3.py`` |
-| ``fused_fp8`` | inference, fp8 mode with nc_fp8, symmetric square (3,3)/(<=16,1) | ``nc_fused_k3_f8`` (csrc/nc_fused.hip) | ``test_gpu_kernels.py`` |
-| ``fused`` | inference, (3,3)/(<=16,1), not all-fp8 | ``nc_fused_k3`` (hidden layer in LDS) | ``test_gpu_kernels.py``, ``test_gpu_fusion.py`` |
-| ``fp8`` | inference, fp8 mode, other 1 -> 16 -> 1 stacks | ``neigh_consensus_fp8`` (e4m3 Conv4d) | ``test_gpu_kernels.py`` |
-| ``bf16_padded`` / ``bf16`` | everything else (training) | ``NeighConsensusPaddedFn`` / ``NeighConsensusFn`` | ``test_gpu_kernels.py``, ``test_gpu_nc_stages.py`` |
+| ``x3_inference`` | precision fp32 / mixed, no autograd | ``nc/x3.py neigh_consensus_x3`` (bf16x3 splits) | ``test_gpu_x3.py`` |
+| ``mixed`` | precision mixed, autograd, fast-path shapes | ``nc/x3.py NeighConsensusMixedFn`` (x3 forward, bf16 backward) | ``test_gpu_x3.py`` |
+| ``x3_fused`` / ``x3`` | precision fp32 (or mixed off the fast shapes), autograd | ``nc/x3.py NeighConsensusX3FusedFn`` / ``NeighConsensusX3Fn`` | ``test_gpu_x3.py`` |
+| ``fused_fp8`` | inference, fp8 mode with nc_fp8, symmetric square (3,3)/(<=16,1) | ``nc/fused.py neigh_consensus_fused_x2_fp8`` (``nc_fused_k3_f8``, csrc/nc_fused.hip) | ``test_gpu_kernels.py`` |
+| ``fused`` | inference, (3,3)/(<=16,1), not all-fp8 | ``nc/fused.py neigh_consensus_fused`` (``nc_fused_k3``, hidden layer in LDS) | ``test_gpu_kernels.py``, ``test_gpu_fusion.py`` |
+| ``fp8`` | inference, fp8 mode, other 1 -> 16 -> 1 stacks | ``nc/fp8.py neigh_consensus_fp8`` (e4m3 Conv4d) | ``test_gpu_kernels.py`` |
+| ``bf16_padded`` / ``bf16`` | everything else (training) | ``nc/train.py NeighConsensusPaddedFn`` / ``NeighConsensusFn`` | ``test_gpu_kernels.py``, ``test_gpu_nc_stages.py`` |
 """
 from __future__ import annotations
 
-import contextlib
-import functools
-
-import numpy as np
 import torch
-import torch.utils.weak as _weak
 
 from .. import config as _config
 from . import _ext
 from . import reference as ref
-from .packing import (_blk_packed, _cout1_packed, _w16_dgrad, _w1x_dgrad, blk_out_weights, gather_pack, ij_groups, ij_in_grad,
-                      ij_in_weights, ij_out_grad, ij_out_weights, pack_w16, pack_w1x, pack_w16_planes, packed_weights,
-                      plane_dgrad_weights, transpose_for_dgrad)
-
-HIP_KS = (1, 3, 5, 7)
-# Cout=1 layers with <= 16 input channels run in output-plane-block mode
-# (conv16_blk_fwd); False selects the ij encoding + ijsum instead (A/B tests
-# and scripts/kbench.py set the module attribute; no environment knob).
-BLK_1OUT = True
-
-
-def nblocks(c: int) -> int:
-    return (c + 15) // 16
-
-
-def layer_kinds(channels, kernel_sizes):
-    """Per layer ``"1in"`` (Cin=1 -> Cout>1), ``"16"`` (Cin>1 -> Cout>1),
-    ``"1out"`` (Cin>1 -> Cout=1) or ``"11"`` (1 -> 1); None if some kernel
-    size has no HIP kernel (only odd sizes 1..7 do)."""
-    kinds, cin = [], 1
-    for c, k in zip(channels, kernel_sizes):
-        if k not in HIP_KS or c < 1:
-            return None
-        kinds.append("11" if cin == 1 and c == 1 else "1in" if cin == 1 else "1out" if c == 1 else "16")
-        cin = c
-    return kinds
-
-
-_V4_PLANES = {5: (15, 20, 25, 30), 3: (15, 20, 25, 30)}     # wgrad16v4 instantiations (K == L)
-
-
-def wgrad_v3_ok(shape, ks: int) -> bool:
-    """wgrad16v3 (sliding G ring): KS 3/5, full-width X rows L + ks - 1 <= 32;
-    or a compile-time wgrad16v4 plane (30 x 30 stages its 34-voxel rows with
-    two DMA instructions)."""
-    if ks not in (3, 5):
-        return False
-    K, L = shape[3], shape[4]
-    return L + ks - 1 <= 32 or (K == L and K in _V4_PLANES[ks])
-
-
-def wgrad_v3_ntl(K: int, L: int, ks: int) -> int:
-    """(k, l) tiles per plane of wgrad16v3 / v4 (mirrors ncnet_wgrad16v3): ~320
-    voxels per tile; on the k = 5 general kernel, more tiles until the 64-voxel
-    chunk count per half-tile is 1, 2 or 5 (the instantiations that do not spill).
-    The general kernel runs where no v4 plane exists or when the wgrad_v3 A/B
-    switch asks for it and the rows fit (L + ks - 1 <= 32)."""
-    kl = K * L
-    ntl = -(-kl // 320)
-    v4 = K == L and K in _V4_PLANES[ks] and not (_config.RUNTIME.wgrad_v3 and L + ks - 1 <= 32)
-    if ks == 5 and not v4:
-        while (-(-(-(-kl // ntl)) // 64)) not in (1, 2, 5):
-            ntl += 1
-    return ntl
-
-
-# workgroups of the 16 -> 16 weight gradient (grid = groups * ks; partials 2 *
-# groups x 160 K floats, summed afterwards); other targets measured within noise
-_WGRAD_WG_TARGET = 512
-
-
-def wgrad_v3_groups(shape, ks: int) -> int:
-    """Column groups per dj for wgrad16v3: ~2 workgroups per CU, never more
-    than the columns (v, j, tile).  Tile rule mirrors ncnet_wgrad16v3."""
-    V, I, J, K, L = shape[:5]
-    ntl = wgrad_v3_ntl(K, L, ks)
-    ncols = V * J * ntl
-    target = max(1, _WGRAD_WG_TARGET // ks)
-    return max(1, min(target, ncols))
-
-
-def wgrad_groups(ks: int, nitems: int) -> int:
-    """K-split groups of wgrad16v2 in full mode (~3000 workgroups over the
-    KS*KS plane offsets; 120 groups at KS=5 beat 20 by 1.4x on MI355X)."""
-    target = max(1, 3072 // (ks * ks))
-    return max(1, min(target, nitems))
-
-
-def wgrad_plane_groups(nitems: int) -> int:
-    """Groups of the plane-only wgrad (grid = groups): ~3 workgroups per CU."""
-    return max(1, min(768, nitems))
-
-
-def _nitems(shape) -> int:
-    V, I, J, K, L = shape[:5]
-    return V * I * J * ((K + 24) // 25) * ((L + 24) // 25)
-
-
-def _wgrad16_launch(C, x16: torch.Tensor, g16: torch.Tensor, ks: int, plane_only: bool):
-    """Unreduced partials (part [2 ng, dd, tap, ci, co], partb [2 ng, 16]) of a 16 -> 16 block."""
-    shape = x16.shape[:5]
-    if plane_only:
-        variant, ng = 2, wgrad_plane_groups(_nitems(shape))
-    elif wgrad_v3_ok(shape, ks):
-        variant, ng = 3, wgrad_v3_groups(shape, ks)
-    else:
-        variant, ng = 2, wgrad_groups(ks, _nitems(shape))
-    ndd = 1 if plane_only else ks * ks
-    part = torch.empty((2 * ng, ndd, ks * ks, 16, 16), dtype=torch.float32, device=x16.device)
-    partb = torch.empty((2 * ng, 16), dtype=torch.float32, device=x16.device)
-    C.wgrad16(x16, g16, part, partb, ks, 2 if plane_only else 0, variant)
-    return part, partb
-
-
-def wgrad16_partials(C, x16: torch.Tensor, g16: torch.Tensor, ks: int, plane_only: bool):
-    """Weight-gradient partials of a 16 -> 16 block and their reduction.
-
-    ``plane_only`` False: all (di, dj) plane offsets (wgrad16v3 when it fits,
-    else wgrad16v2); True: the (P, P) plane only (ij-encoded 1-channel layers,
-    wgrad16v2).  Returns (s, sb): s [dd, tap, ci, co], sb [16] = sum of g16
-    over all voxels (bias gradient, the kernels' ones-MFMA)."""
-    part, partb = _wgrad16_launch(C, x16, g16, ks, plane_only)
-    return part.sum(0), partb.sum(0)
-
-
-def wgrad16_ckpt(C, x16: torch.Tensor, g16: torch.Tensor, ks: int):
-    """The 16 -> 16 layer's weight gradient straight in the checkpoint layout
-    [k, 16, 16, k, k, k] and its bias gradient [16]: the partials of every
-    workgroup reduced and permuted by ONE reduce_cols launch (was two torch
-    reductions, the std permute and the checkpoint permute)."""
-    part, partb = _wgrad16_launch(C, x16, g16, ks, False)
-    dw, db = reduce_partials([
-        (part, ("w16", ks), lambda t: ref.conv4d_weight_from_std(_reduce_wgrad16(t, ks, 16, 16))),
-        (partb, None, None)])
-    return dw, db
-
-
-# reduce_partials plans: (key, device) -> (int32 map [N], output shape)
-_RED_PLANS: dict = {}
-
-
-def _col_map(key, part_shape, fn, device):
-    """Scatter map of a layout function: position in fn's output of every
-    source column (-1: dropped by a slice), from fn applied to the column ids."""
-    k = (key, tuple(part_shape), str(device))
-    ent = _RED_PLANS.get(k)
-    if ent is None:
-        n = 1
-        for d in part_shape:
-            n *= d
-        out = fn(torch.arange(n, dtype=torch.int64).reshape(part_shape))
-        m = torch.full((n,), -1, dtype=torch.int64)
-        m[out.reshape(-1)] = torch.arange(out.numel(), dtype=torch.int64)
-        ent = (m.to(torch.int32).to(device), tuple(out.shape))
-        _RED_PLANS[k] = ent
-    return ent
-
-
-def reduce_partials(segs):
-    """segs: [(part [R, ...] fp32, key, fn)] -> [fn(part.sum(0))] (fn None: the
-    plain sum).  ``fn`` is a layout-only function (permute / reshape / flip /
-    slice) and ``key`` names it for the plan cache.  On the GPU every segment
-    is reduced, laid out and written in ONE reduce_cols launch (fixed summation
-    order: the same bits on every run); on the CPU the same by torch ops."""
-    outs, srcs, dsts, idxs = [], [], [], []
-    for part, key, fn in segs:
-        R = part.shape[0]
-        src = part.reshape(R, -1)
-        if fn is None:
-            idx, shape = None, tuple(part.shape[1:])
-        else:
-            idx, shape = _col_map(key, part.shape[1:], fn, part.device)
-        out = torch.empty(shape, dtype=torch.float32, device=part.device)
-        outs.append(out); srcs.append(src); dsts.append(out); idxs.append(idx)
-    if srcs[0].is_cuda and _ext.use_hip(srcs[0]) and hasattr(_ext.ext(), "reduce_cols"):
-        for i in range(0, len(srcs), 4):
-            _ext.ext().reduce_cols(srcs[i:i + 4], dsts[i:i + 4], idxs[i:i + 4])
-    else:
-        for src, out, idx in zip(srcs, dsts, idxs):
-            s = src.sum(0)
-            if idx is None:
-                out.view(-1).copy_(s)
-            else:
-                keep = idx >= 0
-                out.view(-1)[idx[keep].long()] = s[keep]
-    return outs
-
-
-# Plane-only weight gradient of the Cout=1 layer on wgrad16p (double-buffered
-# items, both ij groups of ijpack(g, -1) against one staged X plane: 0.81 ms vs
-# 2 x 0.44 ms at the training shape) when the (k, l) plane is one tile;
-# WGRAD_P = False (module attribute, A/B only) selects the per-group wgrad16v2 calls.  The Cin=1 layer stays
-# on wgrad16v2: with one G operand every X fragment feeds a single MFMA, the
-# kernel is LDS-bound and v2's 2-3 workgroups per CU hide more (1.18 vs 0.89 ms).
-WGRAD_P = True
-
-
-def wgrad_p_ok(shape) -> bool:
-    return WGRAD_P and shape[3] <= 25 and shape[4] <= 25
-
-
-def wgrad16p_partials(C, x7: torch.Tensor, g7: torch.Tensor, ks: int):
-    """x7 [nx, V,I,J,K,L,16], g7 [ng, ...] bf16 with nx == 1 or ng == 1:
-    plane-only partials of every (x, g) pair -> (s [nx*ng, tap, ci, co], sb [nx*ng, 16])."""
-    nx, ng = x7.shape[0], g7.shape[0]
-    if nx * ng > 2:                       # the kernel pairs at most two operands
-        if nx > 1:
-            outs = [wgrad16p_partials(C, x7[i:i + 2], g7, ks) for i in range(0, nx, 2)]
-        else:
-            outs = [wgrad16p_partials(C, x7, g7[i:i + 2], ks) for i in range(0, ng, 2)]
-        return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
-    groups = max(1, min(1024 // (nx * ng), _nitems(x7.shape[1:6])))
-    part = torch.empty((2 * groups, nx * ng, ks * ks, 16, 16), dtype=torch.float32, device=x7.device)
-    partb = torch.empty((2 * groups, nx * ng, 16), dtype=torch.float32, device=x7.device)
-    C.wgrad16p(x7, g7, part, partb, ks)
-    return part.sum(0), partb.sum(0)
-
-
-def _reduce_wgrad16(s: torch.Tensor, ks: int, cout: int, cin: int) -> torch.Tensor:
-    # s [dd, tap, ci, co] -> std [co, ci, di, dj, dk, dl]
-    return s.permute(3, 2, 0, 1).reshape(16, 16, ks, ks, ks, ks)[:cout, :cin]
-
-
-def _std(w_ref: torch.Tensor) -> torch.Tensor:
-    return ref.conv4d_weight_to_std(w_ref).float()
-
-
-def _pad_bias(b: torch.Tensor, n: int) -> torch.Tensor:
-    b = b.float()
-    if b.numel() == n:
-        return b.contiguous()
-    out = b.new_zeros(n)
-    out[: b.numel()] = b
-    return out
-
-
-def _blk(t: torch.Tensor, a: int, n: int) -> slice:
-    return slice(16 * a, min(n, 16 * a + 16))
-
-
-def planar_to_blocks(z: torch.Tensor) -> torch.Tensor:
-    """fp32 planar [C, V, I, J, K, L] -> bf16 channels-last blocks [NB, V, I, J, K, L, 16]."""
-    c = z.shape[0]
-    nb = nblocks(c)
-    if c < 16 * nb:
-        z = torch.cat((z, z.new_zeros((16 * nb - c,) + tuple(z.shape[1:]))))
-    return z.view((nb, 16) + tuple(z.shape[1:])).permute(0, 2, 3, 4, 5, 6, 1).to(torch.bfloat16).contiguous()
-
-
-def blocks_to_ncl(h: torch.Tensor, c: int) -> torch.Tensor:
-    """bf16 blocks [NB, V, I, J, K, L, 16] -> [V, C, I, J, K, L] (a view-based permute)."""
-    nb = h.shape[0]
-    x = h.permute(1, 0, 6, 2, 3, 4, 5).reshape((h.shape[1], nb * 16) + tuple(h.shape[2:6]))
-    return x[:, :c]
-
-
-def _ij_in_planes(w_std: torch.Tensor) -> torch.Tensor:
-    """[co<=16, 1, k^4] -> group-plane weights [G, nq, 64, 8]."""
-    return pack_w16_planes(ij_in_weights(w_std))
-
-
-def _ij_out_planes(w_std: torch.Tensor, nbi: int) -> torch.Tensor:
-    """[1, ci, k^4] -> [G, nbi, nq, 64, 8]: combo group g, input block a."""
-    per = [pack_w16_planes(ij_out_weights(w_std[:, 16 * a:16 * a + 16])) for a in range(nbi)]
-    return torch.stack(per, 1).contiguous()
-
-
-def cout1_taps_ok(shp, ks: int) -> bool:
-    """Does the tap-row Cout=1 kernel (csrc/cout1.hip) cover this layer?
-    (k, l) planes of 25 x 25 (the 400 px training volume), kernel size 5."""
-    return _config.RUNTIME.cout1_taps and ks == 5 and tuple(shp[3:5]) == (25, 25)
-
-
-def conv_layer(h: torch.Tensor, w_std: torch.Tensor, cin: int, cout: int, bias=None, relu: bool = True,
-               mask=None, f32: bool = False, xs=None, wp=None, wt=None) -> torch.Tensor:
-    """One "same" Conv4d on the HIP kernels, any channel counts.
-
-    h: the 1-channel input [V,I,J,K,L] (bf16/fp32) when cin == 1, else bf16
-    blocks [NBi, V,I,J,K,L,16]; ``xs``: ijpack(h, +1) if already built.
-    Output (pre-activation + bias, then ReLU if ``relu``; or * (mask > 0)):
-      f32=False: bf16 blocks [NBo, ...,16] (cout > 1) / fp32 [V,I,J,K,L] (cout == 1)
-      f32=True : fp32 planar [cout, V,I,J,K,L] (cout > 1) / fp32 [V,I,J,K,L].
-    ``mask`` (bf16 blocks like the output, cout > 1, f32=False only) replaces
-    bias/ReLU by the data-gradient epilogue y = acc * (mask > 0).  ``wp``: the
-    layer's packed operand from ``packed_weights`` (single-block 16 -> 16 and
-    output-plane-block Cout=1 layers), else packed here; ``wt``: the tap-row
-    Cout=1 operand (cout1_taps_weights) where cout1_taps_ok."""
-    C = _ext.ext()
-    ks = w_std.shape[-1]
-    shp = tuple(h.shape[:5]) if cin == 1 else tuple(h.shape[1:6])
-    dev = h.device
-    nbo, nbi = nblocks(cout), nblocks(cin)
-    if cin == 1:
-        if xs is None:
-            xs = torch.empty((ij_groups(ks),) + shp + (16,), dtype=torch.bfloat16, device=dev)
-            C.ijpack(h.contiguous(), xs, ks, 1)
-        if cout == 1:                      # 1 -> 1: one output channel of the group-plane conv
-            z = torch.empty((1,) + shp, dtype=torch.float32, device=dev)
-            C.conv16_fwd(xs, _ij_in_planes(w_std), None, None, z, ks, 4)
-            y = z[0]
-            if bias is not None:
-                y = y + bias.float().view(1)
-            return torch.relu(y) if relu else y
-        outs = []
-        for b in range(nbo):
-            wb = _ij_in_planes(w_std[_blk(w_std, b, cout)])
-            outs.append(_epilogue_call(C, xs, wb, bias, b, cout, relu, mask, f32, shp, ks))
-        return _gather(outs, f32, cout)
-    if cout == 1 and nbi == 1 and cout1_taps_ok(shp, ks) and mask is None:
-        # tap rows: the 25 in-plane taps on the MFMA rows, 76 % useful work
-        # (csrc/cout1.hip), the in-plane shift applied once per output plane
-        y = torch.empty(shp, dtype=torch.float32, device=dev)
-        if C.cout1_taps_fwd(h[0], wt if wt is not None else gather_pack(_cout1_packed, w_std),
-                            None if bias is None else bias.float().reshape(1).contiguous(), y, ks, 1 if relu else 0):
-            return y
-    if cout == 1 and nbi == 1 and BLK_1OUT:
-        # output-plane blocks: the 16 MFMA rows are 4x4 output planes, no
-        # combo-planar partials (2.5 GB at the training shape) and no ijsum
-        y = torch.empty(shp, dtype=torch.float32, device=dev)
-        C.conv16_blk_fwd(h[0], wp if wp is not None else gather_pack(_blk_packed, w_std),
-                         None if bias is None else bias.float().reshape(1).contiguous(), y, ks, 1 if relu else 0)
-        return y
-    if cout == 1:                          # ij encoding: combo-planar partials, shift-summed by ijsum
-        G, nq = ij_groups(ks), ks * ks
-        wz = _ij_out_planes(w_std, nbi)
-        z = torch.empty((nq,) + shp, dtype=torch.float32, device=dev)
-        for gi in range(G):
-            C.conv16_fwd(h, wz[gi], None, None, z[16 * gi:min(nq, 16 * gi + 16)], ks, 4)
-        y = torch.empty(shp, dtype=torch.float32, device=dev)
-        C.ijsum(z, None if bias is None else _pad_bias(bias, 1), y, ks, 1 if relu else 0, 1)
-        return y
-    if nbi == 1:
-        outs = [_epilogue_call(C, h[0], wp if (wp is not None and nbo == 1) else
-                               gather_pack(pack_w16, w_std[_blk(w_std, b, cout), :16]), bias, b, cout, relu,
-                               mask, f32, shp, ks) for b in range(nbo)]
-        return _gather(outs, f32, cout)
-    # several input blocks: fp32 partials per (out, in) block pair, summed before the activation
-    outs = []
-    for b in range(nbo):
-        sl = _blk(w_std, b, cout)
-        nco = sl.stop - sl.start
-        acc = None
-        for a in range(nbi):
-            z = torch.empty((nco,) + shp, dtype=torch.float32, device=dev)
-            C.conv16_fwd(h[a], pack_w16(w_std[sl, 16 * a:16 * a + 16]), None, None, z, ks, 4)
-            acc = z if acc is None else acc.add_(z)
-        if bias is not None and mask is None:
-            acc += bias[sl].float().view(-1, 1, 1, 1, 1, 1)
-        if mask is not None:
-            acc = acc * (blocks_to_ncl(mask[b:b + 1], nco).transpose(0, 1) > 0)
-        elif relu:
-            acc = torch.relu_(acc)
-        outs.append(acc)
-    z = torch.cat(outs) if len(outs) > 1 else outs[0]
-    return z if f32 else planar_to_blocks(z)
-
-
-def _epilogue_call(C, x, wp, bias, b, cout, relu, mask, f32, shp, ks):
-    sl = slice(16 * b, min(cout, 16 * b + 16))
-    nco = sl.stop - sl.start
-    if f32:
-        z = torch.empty((nco,) + shp, dtype=torch.float32, device=x.device)
-        C.conv16_fwd(x, wp, None, None, z, ks, 4)
-        if bias is not None:
-            z += bias[sl].float().view(-1, 1, 1, 1, 1, 1)
-        return torch.relu_(z) if relu else z
-    y = torch.empty(shp + (16,), dtype=torch.bfloat16, device=x.device)
-    if mask is not None:
-        C.conv16_fwd(x, wp, None, mask[b], y, ks, 2)
-    elif relu:
-        bb = torch.zeros(16, device=x.device) if bias is None else _pad_bias(bias[sl], 16)
-        C.conv16_fwd(x, wp, bb, None, y, ks, 1)
-    else:
-        if bias is not None:
-            raise RuntimeError("internal: bf16 output without ReLU takes no bias")
-        C.conv16_fwd(x, wp, None, None, y, ks, 0)
-    return y
-
-
-def _gather(outs, f32: bool, cout: int):
-    if f32:
-        return torch.cat(outs) if len(outs) > 1 else outs[0]
-    return torch.stack(outs) if len(outs) > 1 else outs[0].unsqueeze(0)
-
-
-# ---------------------------------------------------------------------------
-# Padded-plane 1-channel layers (csrc/conv1x.hip) for the NC-Net training stack
-# [1 -> 16 (k=5), 16 -> 16 ..., 16 -> 1 (k=5)] at a 25 x 25 (k, l) plane: the
-# 1-channel operands (the NC input, the last layer's output gradient) are kept
-# as zero-padded planes (0.07 GB) instead of the 16x ij-packed copies (1.6 GB
-# each): the first layer's forward and the last layer's data gradient run on
-# conv1x16, both weight gradients on wgrad1x16.
-
-FAST1X = True    # module attribute (A/B tests, scripts/kbench.py); no environment knob
-# (kernel size, K, L) with conv1x16 / wgrad1x16 instantiations (csrc/conv1x.hip):
-# --image_size 400 and 320 at k = 5, and the IVD recipe's k = 3 at 400 px
-FAST1X_SHAPES = frozenset({(5, 25, 25), (5, 20, 20), (5, 30, 30), (3, 25, 25)})
-
-
-def fast1x_ok(kinds, channels, kernel_sizes, x: torch.Tensor, symmetric: bool) -> bool:
-    if not (FAST1X and x.is_cuda and len(kinds) >= 2 and kinds[0] == "1in" and kinds[-1] == "1out"):
-        return False
-    if any(k != "16" for k in kinds[1:-1]) or any(c != 16 for c in channels[:-1]):
-        return False
-    _, _, I, J, K, L = x.shape
-    if symmetric and (I, J) != (K, L):
-        return False
-    return (kernel_sizes[0], K, L) in FAST1X_SHAPES and (kernel_sizes[-1], K, L) in FAST1X_SHAPES
-
-
-@functools.lru_cache(maxsize=None)
-def _num_cus(index: int) -> int:
-    return torch.cuda.get_device_properties(index).multi_processor_count
-
-
-def _pad_1ch(x3: torch.Tensor, I2: int, J2: int, ks: int, trans: int, out: torch.Tensor | None = None) -> torch.Tensor:
-    """x3 [V, R, C] (fp32 / bf16) -> zero-padded bf16 planes [N, PPL] (csrc/conv1x.hip
-    pad_planes; trans 1: the planes of the A<->B-swapped volume)."""
-    C = _ext.ext()
-    _, ppl = C.pad_geom(I2, J2, ks)
-    n = x3.shape[0] * (x3.shape[2] if trans else x3.shape[1])
-    if out is None:
-        out = torch.zeros((n, ppl), dtype=torch.bfloat16, device=x3.device)
-    C.pad_planes(x3.contiguous(), out, I2, J2, ks, trans)
-    return out
-
-
-def _wgrad1x(C, d16: torch.Tensor, xp: torch.Tensor, ks: int, bias: bool, ch: int, first: bool):
-    """wgrad1x16 partials reduced straight into the checkpoint layout by one
-    reduce_cols launch: R[tap (dk, dl)][combo (di, dj)][c] (the kernel's
-    partial layout, combos padded to 32) becomes
-      first layer (Cin = 1):  dW[co = c, 0, di, dj, dk, dl] = R  -> [k, ch, 1, k, k, k];
-      Cout = 1 last layer:    dW[0, ci = c, t] = R[2P - t] (all four axes
-                              flipped)                          -> [k, 1, ch, k, k, k];
-    and the bias sum [16] (or None) in the same launch."""
-    G = _num_cus(d16.device.index)
-    part = torch.empty((G, ks * ks, 32, 16), dtype=torch.float32, device=d16.device)
-    partb = torch.empty((G, 16), dtype=torch.float32, device=d16.device) if bias else None
-
-    def layout(t):
-        r = t[:, : ks * ks, :ch].reshape((ks,) * 4 + (ch,))          # [dk, dl, di, dj, c]
-        if first:
-            return r.permute(2, 4, 3, 0, 1).unsqueeze(2)
-        return r.flip(0, 1, 2, 3).permute(2, 4, 3, 0, 1).unsqueeze(1)
-
-    C.wgrad1x16(d16, xp, part, partb, ks)
-    segs = [(part, ("w1x", ks, ch, first), layout)]
-    if bias:
-        segs.append((partb, None, None))
-    outs = reduce_partials(segs)
-    return outs[0], (outs[1][:ch] if bias else None)
-
-
-def _stack_fwd(x0: torch.Tensor, ws, bs, kinds, save: list, xp=None, shp=None, packs=None):
-    """x0: [V,I,J,K,L] bf16 -> last layer's ReLU output, fp32: [V,I,J,K,L] if it
-    has one channel, else planar [C, V,I,J,K,L].  Appends, per layer, what its
-    backward reads: the ij-packed input (1-channel inputs) or the bf16 input blocks.
-    ``packs``: {("f", layer): packed forward operand} from ``_stack_packs``."""
-    C = _ext.ext()
-    h = x0
-    nl = len(kinds)
-    cin = 1
-    for li, (w_ref, b) in enumerate(zip(ws, bs)):
-        w = _std(w_ref)
-        ks, cout = w.shape[-1], w.shape[0]
-        last = li == nl - 1
-        xs = None
-        if li == 0 and xp is not None:      # padded-plane first layer (fast1x_ok)
-            y = torch.empty(tuple(shp) + (16,), dtype=torch.bfloat16, device=xp.device)
-            C.conv1x16(xp, packs[("f", 0)] if packs else gather_pack(pack_w1x, w), _pad_bias(b, 16), None, y, ks, 1)
-            save.append(xp)
-            h, cin = y.unsqueeze(0), cout
-            continue
-        if cin == 1:
-            xs = torch.empty((ij_groups(ks),) + tuple(h.shape) + (16,), dtype=torch.bfloat16, device=h.device)
-            C.ijpack(h.contiguous(), xs, ks, 1)
-            save.append((xs, h) if li > 0 else xs)   # mid-stack 1-channel inputs also serve as ReLU masks
-        else:
-            save.append(h)
-        y = conv_layer(h, w, cin, cout, bias=b, relu=True, f32=last and cout > 1, xs=xs,
-                       wp=packs.get(("f", li)) if packs else None, wt=packs.get(("t", li)) if packs else None)
-        if cout == 1 and not last:
-            y = y.to(torch.bfloat16)
-        h = y
-        cin = cout
-    return h
-
-
-# Weight gradients of the layers after the first on a second HIP stream
-# (config.RUNTIME.bwd_overlap, NCNET_BWD_OVERLAP=0 disables): they depend only on the layer input and the
-# incoming gradient, so wgrad(l) runs while the data-gradient chain continues
-# on the main stream (dgrad(l) -> dgrad(l-1) -> ...).  The first layer's
-# weight gradient stays on the main stream, which is idle by then.
-_SIDE_STREAMS: dict = {}
-
-
-def _side_stream(dev: torch.device):
-    st = _SIDE_STREAMS.get(dev.index)
-    if st is None:
-        st = _SIDE_STREAMS[dev.index] = torch.cuda.Stream(device=dev)
-    return st
-
-
-# side-stream inputs kept alive until the backward joins the side stream back
-# (_join_side).  Not record_stream: a block marked in use by the side stream
-# is reusable only once the allocator sees the side stream's event complete --
-# with the host a step ahead of the GPU that is never in time, so every step
-# hipMalloc'ed fresh blocks for its 16-channel volumes (reserved memory grew
-# to the whole 288 GB at a per-GPU batch of 256 and the allocator's
-# release-and-retry stalled whole steps for seconds).  Freed on the host after
-# main.wait_stream(side), the blocks return to main's pool, where every later
-# use is ordered after the side stream's reads.
-_SIDE_KEEP: dict = {}
-
-
-def _join_side(main, side):
-    main.wait_stream(side)
-    _SIDE_KEEP.pop(id(side), None)
-
-
-class _OnSide:
-    """Run a block on the side stream after everything queued on ``main``;
-    inputs stay referenced until _join_side, outputs are marked in use by ``main``."""
-
-    def __init__(self, main, side, inputs):
-        self.main, self.side, self.inputs = main, side, inputs
-        self.ctx = None
-
-    def __enter__(self):
-        if self.side is None:
-            return self
-        self.side.wait_stream(self.main)
-        _SIDE_KEEP.setdefault(id(self.side), []).extend(self.inputs)
-        self.ctx = torch.cuda.stream(self.side)
-        self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
-        return False
-
-
-def _layer_wgrad(C, kind, xin, g, gs, ks, cin, cout):
-    """dW [cout, cin, k^4] (std) and db [cout] of one layer.  xin: ij-packed
-    input (cin == 1) or input blocks; g: gradient w.r.t. the pre-activation
-    (blocks, or 1-channel); gs = ijpack(g, -1) for 1-channel outputs."""
-    G = ij_groups(ks)
-    dev = g.device
-    if kind == "1in":
-        dw = torch.empty((cout, 1) + (ks,) * 4, device=dev)
-        db = torch.empty(cout, device=dev)
-        for b in range(nblocks(cout)):
-            sl = slice(16 * b, min(cout, 16 * b + 16))
-            parts = [wgrad16_partials(C, xin[gi], g[b], ks, True) for gi in range(G)]
-            dw[sl] = ij_in_grad(torch.stack([p[0][0] for p in parts]), sl.stop - sl.start)
-            db[sl] = parts[0][1][:sl.stop - sl.start]
-        return dw, db
-    if kind == "16":
-        dw = torch.empty((cout, cin) + (ks,) * 4, device=dev)
-        db = torch.empty(cout, device=dev)
-        for b in range(nblocks(cout)):
-            so = slice(16 * b, min(cout, 16 * b + 16))
-            for a in range(nblocks(cin)):
-                si = slice(16 * a, min(cin, 16 * a + 16))
-                sw, sb = wgrad16_partials(C, xin[a], g[b], ks, False)
-                dw[so, si] = _reduce_wgrad16(sw, ks, so.stop - so.start, si.stop - si.start)
-                if a == 0:
-                    db[so] = sb[:so.stop - so.start]
-        return dw, db
-    qc = (ks // 2) * ks + ks // 2        # combo (P, P): its channel of ijpack(g, -1) is g itself
-    if kind == "1out":
-        dw = torch.empty((1, cin) + (ks,) * 4, device=dev)
-        db = None
-        for a in range(nblocks(cin)):
-            si = slice(16 * a, min(cin, 16 * a + 16))
-            if wgrad_p_ok(gs.shape[1:6]):
-                s, sb = wgrad16p_partials(C, xin[a:a + 1], gs, ks)
-                dw[:, si] = ij_out_grad(s, si.stop - si.start)
-                if a == 0:
-                    db = sb[qc // 16][qc % 16].reshape(1)
-                continue
-            parts = [wgrad16_partials(C, xin[a], gs[gi], ks, True) for gi in range(G)]
-            dw[:, si] = ij_out_grad(torch.stack([p[0][0] for p in parts]), si.stop - si.start)
-            if a == 0:
-                db = parts[qc // 16][1][qc % 16].reshape(1)
-        return dw, db
-    # "11": the 1-channel gradient as channel 0 of a 16-channel operand
-    g16 = torch.zeros(tuple(g.shape) + (16,), dtype=torch.bfloat16, device=dev)
-    g16[..., 0] = g
-    parts = [wgrad16_partials(C, xin[gi], g16, ks, True) for gi in range(G)]
-    return ij_in_grad(torch.stack([p[0][0] for p in parts]), 1), parts[0][1][:1].clone()
-
-
-def _stack_bwd(g_last: torch.Tensor, saved, ws, kinds, channels, need_dx0: bool, fast1x: bool = False,
-               packs=None, saved_lo=None):
-    """g_last: grad w.r.t. the last conv's PRE-activation, bf16: [V,I,J,K,L] for
-    a 1-channel output, else blocks [NB, V,I,J,K,L,16].
-    Returns (dW list in checkpoint layout, db list, grad of x0 fp32 or None).
-    ``saved_lo`` (nc_precision='mixed', fast1x only): per layer the lo part of
-    a bf16x3-split forward input; each weight gradient then adds the
-    (X_lo, G) product to the (X_hi, G) one (G bf16)."""
-    C = _ext.ext()
-    nl = len(kinds)
-    dws, dbs = [None] * nl, [None] * nl
-    ref_layout = [False] * nl          # True: dW already in the checkpoint layout
-    g = g_last
-    gx0 = None
-    main = side = None
-    if _config.RUNTIME.bwd_overlap and g_last.is_cuda:
-        main = torch.cuda.current_stream(g_last.device)
-        side = _side_stream(g_last.device)
-    for li in range(nl - 1, -1, -1):
-        kind = kinds[li]
-        w = _std(ws[li])
-        ks = w.shape[-1]
-        cout = channels[li]
-        cin = 1 if li == 0 else channels[li - 1]
-        sv = saved[li]
-        if cin == 1:
-            xin, hin = (sv if li > 0 else (sv, None))
-        else:
-            xin = hin = sv
-        gs = None
-        if fast1x and kind in ("1in", "1out"):
-            if kind == "1out":                       # padded planes of the 1-channel output gradient
-                gp = _pad_1ch(g.reshape(g.shape[0], g.shape[1] * g.shape[2], g.shape[3] * g.shape[4]),
-                              g.shape[3], g.shape[4], ks, 0)
-                xlo = saved_lo[li] if saved_lo is not None else None
-                with _OnSide(main if li > 0 else None, side if li > 0 else None,
-                             (xin, g, gp) + ((xlo,) if xlo is not None else ())):
-                    dw, _ = _wgrad1x(C, xin[0], gp, ks, False, cin, False)
-                    if xlo is not None:
-                        dw = dw + _wgrad1x(C, xlo[0], gp, ks, False, cin, False)[0]
-                    db = g.sum(dtype=torch.float32).reshape(1)
-                if li > 0 or need_dx0:
-                    gn = torch.empty((1,) + tuple(hin.shape[1:]), dtype=torch.bfloat16, device=g.device)
-                    C.conv1x16(gp, packs[("b", li)] if packs else gather_pack(_w1x_dgrad, w), None, hin[0], gn[0],
-                               ks, 2)
-                    g = gn
-            else:                                    # first layer: xin = padded NC-input planes
-                dw, db = _wgrad1x(C, g[0], xin, ks, True, cout, True)
-                if saved_lo is not None:
-                    dw = dw + _wgrad1x(C, g[0], saved_lo[li], ks, False, cout, True)[0]
-                if need_dx0:
-                    gx0 = conv_layer(g, transpose_for_dgrad(w), cout, 1, relu=False)
-            dws[li] = dw
-            dbs[li] = db
-            ref_layout[li] = True
-            continue
-        if cout == 1 and kind == "1out":
-            gs = torch.empty((ij_groups(ks),) + tuple(g.shape) + (16,), dtype=torch.bfloat16, device=g.device)
-            C.ijpack(g, gs, ks, -1)                  # adjoint of ijsum: shared by wgrad and dgrad
-        on_side = li > 0
-        xlo = saved_lo[li] if saved_lo is not None else None
-        with _OnSide(main if on_side else None, side if on_side else None,
-                     tuple(t for t in (xin, g, gs, xlo) if t is not None)):
-            if kind == "16" and cin == 16 and cout == 16:
-                # one reduce_cols launch: partials -> checkpoint layout + bias
-                dw, db = wgrad16_ckpt(C, xin[0], g[0], ks)
-                if xlo is not None:
-                    dw = dw + wgrad16_ckpt(C, xlo[0], g[0], ks)[0]
-                ref_layout[li] = True
-            else:
-                dw, db = _layer_wgrad(C, kind, xin, g, gs, ks, cin, cout)
-        if li > 0 or need_dx0:
-            if kind == "1out":                       # reuses ijpack(g, -1) of the weight gradient
-                # each input block's gradient is written straight into its slot
-                # (no stacking copy of the [NB, V,I,J,K,L,16] result)
-                gn = torch.empty((nblocks(cin),) + tuple(hin.shape[1:]), dtype=torch.bfloat16, device=g.device)
-                for a in range(nblocks(cin)):
-                    wp = pack_w16_planes(plane_dgrad_weights(ij_out_weights(w[:, 16 * a:16 * a + 16])))
-                    C.conv16_fwd(gs, wp, None, hin[a], gn[a], ks, 2)
-                g = gn
-            elif cin == 1:                           # gradient w.r.t. a 1-channel input (fp32)
-                gx = conv_layer(g, transpose_for_dgrad(w), cout, 1, relu=False)
-                if li == 0:
-                    gx0 = gx
-                else:                                # mid-stack: the previous layer's ReLU mask
-                    g = (gx * (hin > 0)).to(torch.bfloat16)
-            else:                                    # "16": masked by the previous layer's ReLU output
-                g = conv_layer(g, transpose_for_dgrad(w), cout, cin, relu=False, mask=hin,
-                               wp=packs.get(("b", li)) if packs else None)
-        dws[li] = dw
-        dbs[li] = db
-    if side is not None:
-        _join_side(main, side)
-        for t in dws + dbs:          # produced on the side stream, consumed (and freed) on main
-            t.record_stream(main)
-    return [d if ref_layout[i] else ref.conv4d_weight_from_std(d) for i, d in enumerate(dws)], dbs, gx0
-
-
-def _stack_packs(ws, kinds):
-    """Every packed operand of the padded-plane training stack (fast1x_ok) --
-    conv1x16 weights of layer 0, conv16 weights of the 16 -> 16 layers and their
-    data-gradient (transposed, flipped) weights, the output-plane-block weights
-    of the Cout=1 layer and its conv1x16 data-gradient weights -- from ONE gather
-    launch (packing.packed_weights) -> {("f" | "b", layer): bf16 tensor}."""
-    specs, keys = [], []
-    nl = len(kinds)
-    for li, kind in enumerate(kinds):
-        if li == 0:
-            specs.append((0, pack_w1x)); keys.append(("f", 0))
-        elif li == nl - 1:
-            specs += [(li, _blk_packed), (li, _cout1_packed), (li, _w1x_dgrad)]
-            keys += [("f", li), ("t", li), ("b", li)]
-        else:
-            specs += [(li, pack_w16), (li, _w16_dgrad)]; keys += [("f", li), ("b", li)]
-    return dict(zip(keys, packed_weights(list(ws), specs)))
-
-
-def _swap_flat(x: torch.Tensor, shape_ab):
-    """[V, I*J, K*L] -> [V, K*L, I*J] via the HIP tiled transpose."""
-    C = _ext.ext()
-    V = x.shape[0]
-    i, j, k, l = shape_ab
-    out = torch.empty((V, k * l, i * j), dtype=x.dtype, device=x.device)
-    C.transpose(x.reshape(V, i * j, k * l), out)
-    return out
-
-
-def _combine_multi(z1: torch.Tensor, z2: torch.Tensor, dims) -> torch.Tensor:
-    """Symmetric combine of multi-channel outputs: z1 planar [C, V, I, J, K, L],
-    z2 planar [C, V, K, L, I, J] -> y [V, C, I, J, K, L] fp32."""
-    return (z1 + z2.permute(0, 1, 4, 5, 2, 3)).transpose(0, 1).contiguous()
-
-
-class NeighConsensusFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, symmetric, kinds, channels, *params):
-        return NeighConsensusFn._fwd(ctx, x, symmetric, kinds, channels, params)
-
-    @staticmethod
-    def _fwd(ctx, x, symmetric, kinds, channels, params, xp_in=None):
-        """``xp_in``: the padded bf16 planes of both symmetric branches, already
-        written by MutualMatching (mutual.mutual_matching_padded); only used
-        on the padded-plane path (fast1x_ok, symmetric, square)."""
-        ws, bs = params[0::2], params[1::2]
-        V, _, I, J, K, L = x.shape
-        R, Cc = I * J, K * L
-        cl = channels[-1]
-        saved_layers = []
-        square = (I, J) == (K, L)
-        fast = fast1x_ok(kinds, channels, [w.shape[0] for w in ws], x, symmetric)
-        packs = _stack_packs(ws, kinds) if fast and BLK_1OUT else None
-        if fast:
-            # the 1-channel input as padded planes, both branches in one batch
-            # (pad_planes trans=1 writes the swapped branch's planes directly)
-            x3 = x.reshape(V, R, Cc)
-            k0 = ws[0].shape[0]
-            if symmetric:
-                _, ppl = _ext.ext().pad_geom(K, L, k0)
-                if xp_in is not None and tuple(xp_in.shape) == (2 * V * R, ppl) and xp_in.dtype == torch.bfloat16:
-                    xp = xp_in
-                else:
-                    xp = torch.zeros((2 * V * R, ppl), dtype=torch.bfloat16, device=x.device)
-                    _pad_1ch(x3, K, L, k0, 0, out=xp[:V * R])
-                    _pad_1ch(x3, I, J, k0, 1, out=xp[V * R:])
-                z = _stack_fwd(None, ws, bs, kinds, saved_layers, xp=xp, shp=(2 * V, I, J, K, L), packs=packs)
-            else:
-                z = _stack_fwd(None, ws, bs, kinds, saved_layers, xp=_pad_1ch(x3, K, L, k0, 0), shp=(V, I, J, K, L),
-                               packs=packs)
-            branches = [saved_layers]
-        elif symmetric:
-            xb = x.reshape(V, I, J, K, L).to(torch.bfloat16).contiguous()
-            xt = _swap_flat(xb.reshape(V, R, Cc), (I, J, K, L)).reshape(V, K, L, I, J)
-            if square:
-                z = _stack_fwd(torch.cat((xb, xt), 0), ws, bs, kinds, saved_layers)
-                branches = [saved_layers]
-            else:
-                s1, s2 = [], []
-                z1 = _stack_fwd(xb, ws, bs, kinds, s1)
-                z2 = _stack_fwd(xt, ws, bs, kinds, s2)
-                branches = [s1, s2]
-        else:
-            z = _stack_fwd(x.reshape(V, I, J, K, L).to(torch.bfloat16).contiguous(), ws, bs, kinds, saved_layers)
-            branches = [saved_layers]
-        if symmetric:
-            if square:
-                z1, z2 = (z[:V], z[V:]) if cl == 1 else (z[:, :V], z[:, V:])
-            if cl == 1:
-                if not square:
-                    z = torch.cat((z1.reshape(-1), z2.reshape(-1)))
-                y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x.device)
-                _ext.ext().combine_fwd(z.reshape(-1), y, R, Cc)
-                y = y.reshape(V, 1, I, J, K, L)
-            else:
-                if not square:
-                    z = torch.cat((z1.reshape(cl, -1), z2.reshape(cl, -1)), 1)
-                y = _combine_multi(z1, z2, (V, I, J, K, L))
-        else:
-            y = z.reshape(V, 1, I, J, K, L) if cl == 1 else z.transpose(0, 1).contiguous()
-        ctx.fast1x = fast
-        ctx.packs = packs
-        ctx.symmetric = symmetric
-        ctx.kinds = kinds
-        ctx.channels = channels
-        ctx.dims = (V, I, J, K, L)
-        ctx.nbranch = len(branches)
-        flat = []
-        ctx.layout = []
-        for br in branches:
-            lay = []
-            for t in br:
-                if isinstance(t, tuple):
-                    flat.extend(t)
-                    lay.append(2)
-                else:
-                    flat.append(t)
-                    lay.append(1)
-            ctx.layout.append(lay)
-        ctx.save_for_backward(z, *params, *flat)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        gx, grads = NeighConsensusFn._bwd(ctx, gy)
-        return (gx, None, None, None, *grads)
-
-    @staticmethod
-    def _bwd(ctx, gy):
-        z, *rest = ctx.saved_tensors
-        nparam = 2 * len(ctx.kinds)
-        params, flat = rest[:nparam], list(rest[nparam:])
-        ws = params[0::2]
-        V, I, J, K, L = ctx.dims
-        R, Cc = I * J, K * L
-        cl = ctx.channels[-1]
-        need_dx0 = ctx.needs_input_grad[0]
-        branches = []
-        pos = 0
-        for lay in ctx.layout:
-            br = []
-            for n in lay:
-                br.append(flat[pos] if n == 1 else tuple(flat[pos:pos + n]))
-                pos += n
-            branches.append(br)
-        if cl == 1:
-            gy3 = gy.reshape(V, R, Cc).float().contiguous()
-            if ctx.symmetric:
-                gz = torch.empty(z.numel(), dtype=torch.bfloat16, device=gy.device)
-                _ext.ext().combine_bwd(gy3, z, gz, R, Cc)
-            else:
-                gz = (gy3.reshape(-1) * (z.reshape(-1) > 0)).to(torch.bfloat16)
-            n1 = V * R * Cc
-            if ctx.nbranch == 1:
-                nv = 2 * V if ctx.symmetric else V
-                gl = [gz.reshape(nv, I, J, K, L)]
-            else:
-                gl = [gz[:n1].reshape(V, I, J, K, L), gz[n1:].reshape(V, K, L, I, J)]
-        else:
-            g1 = gy.float().transpose(0, 1)                        # planar [C, V, I, J, K, L]
-            if ctx.symmetric:
-                g2 = g1.permute(0, 1, 4, 5, 2, 3)                  # [C, V, K, L, I, J]
-                zz = z.reshape(cl, -1)
-                n1 = V * R * Cc
-                gz1 = g1.reshape(cl, -1) * (zz[:, :n1] > 0)
-                gz2 = g2.reshape(cl, -1) * (zz[:, n1:] > 0)
-                if ctx.nbranch == 1:
-                    gl = [planar_to_blocks(torch.cat((gz1, gz2), 1).reshape(cl, 2 * V, I, J, K, L))]
-                else:
-                    gl = [planar_to_blocks(gz1.reshape(cl, V, I, J, K, L)),
-                          planar_to_blocks(gz2.reshape(cl, V, K, L, I, J))]
-            else:
-                gl = [planar_to_blocks(g1 * (z > 0))]
-        res = [_stack_bwd(g, br, ws, ctx.kinds, ctx.channels, need_dx0, ctx.fast1x, ctx.packs)
-               for g, br in zip(gl, branches)]
-        if len(res) == 1:            # one batched branch: no accumulation copies
-            dws, dbs = res[0][0], res[0][1]
-        else:
-            dws = [sum(r[0][i] for r in res) for i in range(len(ws))]
-            dbs = [sum(r[1][i] for r in res) for i in range(len(ws))]
-        gx = None
-        if need_dx0:
-            if ctx.symmetric:
-                if len(res) == 1:
-                    g0 = res[0][2].reshape(-1)
-                    ga, gbt = g0[:V * R * Cc], g0[V * R * Cc:]
-                else:
-                    ga, gbt = res[0][2].reshape(-1), res[1][2].reshape(-1)
-                gb = _swap_flat(gbt.reshape(V, Cc, R), (K, L, I, J))
-                gx = (ga.reshape(V, R, Cc) + gb).reshape(V, 1, I, J, K, L)
-            else:
-                gx = res[0][2].reshape(V, 1, I, J, K, L)
-        grads = []
-        for dw, db in zip(dws, dbs):
-            grads += [dw, db]
-        return gx, grads
-
-
-class NeighConsensusPaddedFn(torch.autograd.Function):
-    """NeighConsensusFn with the padded NC-input planes supplied by the
-    MutualMatching that produced ``x`` (mm_apply's padded mode): the two
-    pad passes and the zero fill of the training step's forward disappear."""
-
-    @staticmethod
-    def forward(ctx, x, xp, symmetric, kinds, channels, *params):
-        return NeighConsensusFn._fwd(ctx, x, symmetric, kinds, channels, params, xp_in=xp)
-
-    @staticmethod
-    def backward(ctx, gy):
-        gx, grads = NeighConsensusFn._bwd(ctx, gy)
-        return (gx, None, None, None, None, *grads)
-
-
-# ---------------------------------------------------------------------------
-# fp32-accurate inference ("bf16x3"): every Conv4d is three bf16 MFMA convs,
-# conv(h, w) ~ conv(h_hi, w_hi) + conv(h_hi, w_lo) + conv(h_lo, w_hi), where
-# x_hi = bf16(x) and x_lo = bf16(x - x_hi), summed in fp32; the activations
-# stay fp32 between layers (split again for the next layer).  This is the
-# reference's fp32 NeighConsensus (lib/conv4d.py:23-24, lib/model.py:110-113)
-# to ~16 mantissa bits, at 3x the bf16 cost; used by ImMatchNet(corr_dtype='fp32').
-
-def _split(t: torch.Tensor):
-    hi = t.to(torch.bfloat16)
-    return hi, (t - hi.float()).to(torch.bfloat16)
-
-
-def _stack_fwd_x3(x0: torch.Tensor, ws, bs, channels) -> torch.Tensor:
-    """x0 fp32 [V,I,J,K,L] -> last layer ReLU output fp32 ([V,...] or planar [C, V, ...])."""
-    h = x0
-    cin = 1
-    for w_ref, b, cout in zip(ws, bs, channels):
-        w = _std(w_ref)
-        w_hi = w.to(torch.bfloat16).float()
-        w_lo = w - w_hi
-        if cin == 1:
-            h_hi, h_lo = _split(h)
-        else:
-            hh, hl = _split(h)                  # planar fp32 [cin, V, ...] -> blocks
-            h_hi, h_lo = planar_to_blocks(hh.float()), planar_to_blocks(hl.float())
-        z = conv_layer(h_hi, w_hi, cin, cout, relu=False, f32=True)
-        z = z + conv_layer(h_hi, w_lo, cin, cout, relu=False, f32=True)
-        z = z + conv_layer(h_lo, w_hi, cin, cout, relu=False, f32=True)
-        bb = b.float().view(-1, *([1] * (z.dim() - 1))) if cout > 1 else b.float().view(1)
-        h = torch.relu(z + bb)
-        cin = cout
-    return h
-
-
-def neigh_consensus_x3(x: torch.Tensor, weights, biases, channels, symmetric: bool = True) -> torch.Tensor:
-    """fp32-accurate inference NeighConsensus on the bf16 MFMA kernels (no autograd)."""
-    V, _, I, J, K, L = x.shape
-    cl = channels[-1]
-    xf = x.reshape(V, I, J, K, L).float().contiguous()
-
-    def as_out(z, shape):
-        return z.reshape((V, 1) + shape) if cl == 1 else z.transpose(0, 1).reshape((V, cl) + shape)
-
-    y = as_out(_stack_fwd_x3(xf, weights, biases, channels), (I, J, K, L))
-    if symmetric:
-        xt = xf.permute(0, 3, 4, 1, 2).contiguous()
-        y2 = as_out(_stack_fwd_x3(xt, weights, biases, channels), (K, L, I, J))
-        y = y + y2.permute(0, 1, 4, 5, 2, 3)
-    return y.contiguous()
-
-
-def _to_repr(t: torch.Tensor, c: int) -> torch.Tensor:
-    """fp32 activation/gradient (1-channel [V,...] or planar [C, V, ...]) -> the
-    layer representation of the bf16 kernels (1-channel bf16 / bf16 blocks)."""
-    return t.to(torch.bfloat16).contiguous() if c == 1 else planar_to_blocks(t)
-
-
-def _split_repr(t: torch.Tensor, c: int):
-    hi = t.to(torch.bfloat16).float()
-    return _to_repr(hi, c), _to_repr(t - hi, c)
-
-
-def _conv_x3(h_hi, h_lo, w: torch.Tensor, cin: int, cout: int) -> torch.Tensor:
-    w_hi = w.to(torch.bfloat16).float()
-    w_lo = w - w_hi
-    z = conv_layer(h_hi, w_hi, cin, cout, relu=False, f32=True)
-    z = z + conv_layer(h_hi, w_lo, cin, cout, relu=False, f32=True)
-    return z + conv_layer(h_lo, w_hi, cin, cout, relu=False, f32=True)
-
-
-def _wgrad_x3(C, kind, h_hi, h_lo, g_hi, g_lo, ks, cin, cout) -> torch.Tensor:
-    """dW = X.G summed as Xhi.Ghi + Xhi.Glo + Xlo.Ghi on the bf16 wgrad kernels."""
-    def xin(h):
-        if cin != 1:
-            return h
-        xs = torch.empty((ij_groups(ks),) + tuple(h.shape) + (16,), dtype=torch.bfloat16, device=h.device)
-        C.ijpack(h, xs, ks, 1)
-        return xs
-
-    def gsp(g):
-        if cout != 1 or kind != "1out":
-            return None
-        gs = torch.empty((ij_groups(ks),) + tuple(g.shape) + (16,), dtype=torch.bfloat16, device=g.device)
-        C.ijpack(g, gs, ks, -1)
-        return gs
-    xh, xl = xin(h_hi), xin(h_lo)
-    dw = _layer_wgrad(C, kind, xh, g_hi, gsp(g_hi), ks, cin, cout)[0]
-    dw = dw + _layer_wgrad(C, kind, xh, g_lo, gsp(g_lo), ks, cin, cout)[0]
-    return dw + _layer_wgrad(C, kind, xl, g_hi, gsp(g_hi), ks, cin, cout)[0]
-
-
-class NeighConsensusX3Fn(torch.autograd.Function):
-    """fp32-accurate TRAINING NeighConsensus: every forward conv, data gradient
-    and weight gradient is a bf16x3 split on the bf16 MFMA kernels (3x the bf16
-    cost), activations and gradients stay fp32 between layers.  The reference
-    trains in fp32 (lib/conv4d.py, train.py); this mode reproduces it where the
-    weak loss's positive/negative signal is below bf16 resolution (random-init
-    trunks, scripts/train_quality.py)."""
-
-    @staticmethod
-    def forward(ctx, x, symmetric, kinds, channels, *params):
-        C = _ext.ext()
-        ws = [_std(w) for w in params[0::2]]
-        bs = params[1::2]
-        V, _, I, J, K, L = x.shape
-        x0 = x.reshape(V, I, J, K, L).float()
-        if symmetric:
-            x0 = torch.cat((x0, x0.permute(0, 3, 4, 1, 2)), 0) if (I, J) == (K, L) else None
-        if x0 is None:
-            raise NotImplementedError("fp32 NC training: symmetric mode needs square volumes")
-        h, cin, saved = x0.contiguous(), 1, []
-        for w, b, cout in zip(ws, bs, channels):
-            hh, hl = _split_repr(h, cin)
-            z = _conv_x3(hh, hl, w, cin, cout)
-            z = z + (b.float().view(-1, *([1] * (z.dim() - 1))) if cout > 1 else b.float().view(1))
-            a = torch.relu(z)
-            saved += [hh, hl, a]
-            h, cin = a, cout
-        ctx.kinds, ctx.channels, ctx.symmetric, ctx.dims = kinds, channels, symmetric, (V, I, J, K, L)
-        ctx.save_for_backward(*params, *saved)
-        cl = channels[-1]
-        y = h.reshape((-1, 1) + tuple(h.shape[1:])) if cl == 1 else h.transpose(0, 1)
-        if symmetric:
-            y1, y2 = y[:V], y[V:]
-            y = y1 + y2.permute(0, 1, 4, 5, 2, 3)
-        return y.contiguous()
-
-    @staticmethod
-    def backward(ctx, gy):
-        C = _ext.ext()
-        nl = len(ctx.kinds)
-        params = ctx.saved_tensors[:2 * nl]
-        saved = ctx.saved_tensors[2 * nl:]
-        ws = [_std(w) for w in params[0::2]]
-        V, I, J, K, L = ctx.dims
-        cl = ctx.channels[-1]
-        g = gy.float()
-        if ctx.symmetric:
-            g = torch.cat((g, g.permute(0, 1, 4, 5, 2, 3)), 0)
-        g = g[:, 0] if cl == 1 else g.transpose(0, 1)        # d/d(last activation), fp32
-        dws, dbs = [None] * nl, [None] * nl
-        gx = None
-        for li in range(nl - 1, -1, -1):
-            hh, hl, a = saved[3 * li:3 * li + 3]
-            cout = ctx.channels[li]
-            cin = 1 if li == 0 else ctx.channels[li - 1]
-            ks = ws[li].shape[-1]
-            gp = g * (a > 0)                                   # d/d(pre-activation)
-            dbs[li] = gp.sum().reshape(1) if cout == 1 else gp.reshape(cout, -1).sum(1)
-            gh, gl = _split_repr(gp, cout)
-            dws[li] = ref.conv4d_weight_from_std(_wgrad_x3(C, ctx.kinds[li], hh, hl, gh, gl, ks, cin, cout))
-            if li > 0 or ctx.needs_input_grad[0]:
-                g = _conv_x3(gh, gl, transpose_for_dgrad(ws[li]), cout, cin)
-        if ctx.needs_input_grad[0]:
-            g = g.reshape(2 * V if ctx.symmetric else V, I, J, K, L) if ctx.symmetric else g.reshape(V, I, J, K, L)
-            if ctx.symmetric:
-                g = g[:V] + g[V:].permute(0, 3, 4, 1, 2)
-            gx = g.reshape(V, 1, I, J, K, L)
-        grads = []
-        for dw, db in zip(dws, dbs):
-            grads += [dw, db]
-        return (gx, None, None, None, *grads)
-
-
-# ---------------------------------------------------------------------------
-# fp32-accurate training on the fused bf16x3 kernels (csrc/conv4d_fwd.hip
-# EPI_X3).  Every activation and gradient between layers is kept as a hi / lo
-# bf16 pair (x = hi + lo to ~16 mantissa bits); each Conv4d is ONE launch that
-# runs the three phases (X_hi, W_hi), (X_hi, W_lo), (X_lo, W_hi) into its fp32
-# accumulators and writes the split result from its epilogue (bias + ReLU, or
-# the previous layer's ReLU mask for data gradients).  Weight gradients are the
-# three (X, G) products on the bf16 wgrad kernels, summed.  Covers the
-# 1 -> (16 ->)* 1 stacks with KS 3 / 5 (every NC-Net config); others use
-# NeighConsensusX3Fn's per-conv path.
-
-# bf16x3 precision ablation (scripts/train_quality.py --x3-drop): stages of the
-# fp32-accurate training path that run in plain bf16 instead (their lo parts
-# zeroed: bf16 x bf16 products accumulated in fp32, exactly the bf16 path's
-# arithmetic), to find which stages the weak-loss signal needs:
-#   corr     the correlation operands (the L2-normalised trunk features)
-#   nc_in    the NeighConsensus input (the MutualMatching output)
-#   nc_w     the NeighConsensus weights
-#   nc_act   the hidden NeighConsensus activations
-#   nc_grad  the backward's activation gradients
-#   nc_w_bwd the NeighConsensus weights in the backward only (data gradients)
-X3_STAGES = ("corr", "nc_in", "nc_w", "nc_act", "nc_grad", "nc_w_bwd")
-_X3_DROP: frozenset = frozenset()
-
-
-@contextlib.contextmanager
-def x3_ablation(stages):
-    """Run the bf16x3 training path with ``stages`` (subset of X3_STAGES) in bf16."""
-    global _X3_DROP
-    bad = set(stages) - set(X3_STAGES)
-    if bad:
-        raise ValueError(f"unknown x3 stages {sorted(bad)}; known: {X3_STAGES}")
-    old, _X3_DROP = _X3_DROP, frozenset(stages)
-    try:
-        yield
-    finally:
-        _X3_DROP = old
-
-
-def x3_dropped(stage: str) -> bool:
-    return stage in _X3_DROP
-
-
-def _x3_weights(ws, backward: bool = False):
-    drop = "nc_w" in _X3_DROP or (backward and "nc_w_bwd" in _X3_DROP)
-    return [w.to(torch.bfloat16).float() for w in ws] if drop else ws
-
-
-def _wsplit(w: torch.Tensor):
-    hi = w.to(torch.bfloat16).float()
-    return hi, w - hi
-
-
-def _pack2(fn, w: torch.Tensor) -> torch.Tensor:
-    """[2, ...] packed weights: the hi set, then the lo set (the kernels' layout)."""
-    hi, lo = _wsplit(w)
-    return torch.stack((fn(hi), fn(lo))).contiguous()
-
-
-def x3_fused_ok(kinds, channels, kernel_sizes, x: torch.Tensor, symmetric: bool) -> bool:
-    I, J, K, L = x.shape[2:6]
-    return (kinds is not None and len(kinds) >= 2 and kinds[0] == "1in" and kinds[-1] == "1out"
-            and all(k == "16" for k in kinds[1:-1]) and max(channels) <= 16
-            and all(k in (3, 5) for k in kernel_sizes) and symmetric and (I, J) == (K, L))
-
-
-def _split_bf16(t: torch.Tensor, out: torch.Tensor):
-    """fp32 t -> out[0] = bf16(t), out[1] = bf16(t - out[0])."""
-    out[0].copy_(t)
-    out[1].copy_(t - out[0].float())
-    return out
-
-
-def _x3_fast1x_layer(C, ctx, li, kind, w, xin, g, dws, dbs, main, side, shp, ks, cin, cout):
-    """Backward of a 1-channel layer of the fused bf16x3 stack on the padded-plane
-    kernels: the weight gradient as the three wgrad1x16 products (X_hi G_hi +
-    X_hi G_lo + X_lo G_hi), the last layer's data gradient as conv1x16's
-    bf16x3 mode with the ReLU mask of its input.  ``g`` [2, 2V, ...(, 16)]: the
-    hi / lo gradient w.r.t. the layer's pre-activation.  Returns the next
-    (lower) layer's pre-activation gradient, or None after the first layer."""
-    V, I, J, K, L = ctx.dims
-    if kind == "1out":
-        n = g.shape[1]
-        gp = torch.zeros((2, n * I * J) + (C.pad_geom(K, L, ks)[1],), dtype=torch.bfloat16, device=g.device)
-        for h in range(2):
-            _pad_1ch(g[h].reshape(n, I * J, K * L), K, L, ks, 0, out=gp[h])
-        with _OnSide(main, side, (xin, g, gp)):
-            # (each product already in the checkpoint layout: the layout is linear)
-            dws[li] = sum(_wgrad1x(C, xin[a], gp[b], ks, False, cin, False)[0] for a, b in ((0, 0), (0, 1), (1, 0)))
-            dbs[li] = (g[0].sum(dtype=torch.float32) + g[1].sum(dtype=torch.float32)).reshape(1)
-        gn = torch.empty((2,) + tuple(shp) + (16,), dtype=torch.bfloat16, device=g.device)
-        C.conv1x16(gp, _pack2(pack_w1x, transpose_for_dgrad(w)), None, xin[0], gn, ks, 2 | 4)
-        return gn
-    # first layer: xin = padded planes of the NC input [2, N, PPL]; g [2, 2V, ..., 16]
-    parts = [_wgrad1x(C, g[a], xin[b], ks, b == 0, cout, True) for a, b in ((0, 0), (1, 0), (0, 1))]
-    dws[li] = parts[0][0] + parts[1][0] + parts[2][0]
-    dbs[li] = parts[0][1] + parts[1][1]
-    return None
-
-
-class NeighConsensusX3FusedFn(torch.autograd.Function):
-    """fp32-accurate TRAINING NeighConsensus (symmetric, square volumes) on the
-    fused bf16x3 kernels; same math as NeighConsensusX3Fn."""
-
-    @staticmethod
-    def forward(ctx, x, kinds, channels, *params):
-        C = _ext.ext()
-        ws = [_std(w) for w in params[0::2]]
-        bs = params[1::2]
-        V, _, I, J, K, L = x.shape
-        R, Cc = I * J, K * L
-        ks0 = ws[0].shape[-1]
-        dev = x.device
-        fast = fast1x_ok(kinds, channels, [w.shape[-1] for w in ws], x, True)
-        if fast:
-            # padded 1-channel planes of hi and lo, both branches (the swapped
-            # one written by pad_planes trans=1): the conv1x16 / wgrad1x16 path
-            x3 = x.reshape(V, R, Cc).float()
-            hi = x3.to(torch.bfloat16)
-            lo = (x3 - hi.float()).to(torch.bfloat16)
-            _, ppl = C.pad_geom(K, L, ks0)
-            xs = torch.zeros((2, 2 * V * R, ppl), dtype=torch.bfloat16, device=dev)
-            for t, part in ((hi, xs[0]), (lo, xs[1])):
-                _pad_1ch(t, K, L, ks0, 0, out=part[:V * R])
-                _pad_1ch(t, I, J, ks0, 1, out=part[V * R:])
-            del x3, hi, lo
-            shp = (2 * V, I, J, K, L)
-        else:
-            x0 = x.reshape(V, I, J, K, L).float()
-            x0 = torch.cat((x0, x0.permute(0, 3, 4, 1, 2)), 0)      # both symmetric branches
-            shp = tuple(x0.shape)
-            xsp = torch.empty((2,) + shp, dtype=torch.bfloat16, device=dev)
-            _split_bf16(x0, xsp)
-            del x0
-            xs = torch.empty((2, ij_groups(ks0)) + shp + (16,), dtype=torch.bfloat16, device=dev)
-            C.ijpack(xsp[0], xs[0], ks0, 1)
-            C.ijpack(xsp[1], xs[1], ks0, 1)
-            del xsp
-        if "nc_in" in _X3_DROP:
-            xs[1].zero_()
-        ws = _x3_weights(ws)
-        saved = [xs]
-        h = None
-        for li, kind in enumerate(kinds):
-            w, b = ws[li], bs[li]
-            ks = w.shape[-1]
-            if kind == "1out":
-                y = torch.empty(shp, dtype=torch.float32, device=dev)
-                C.conv16_blk_fwd_x3(h[0], h[1], _pack2(lambda t: pack_w16_planes(blk_out_weights(t)), w),
-                                    b.float().reshape(1).contiguous(), y, ks, 1)
-                h = y
-                break
-            a = torch.empty((2,) + shp + (16,), dtype=torch.bfloat16, device=dev)
-            if kind == "1in" and fast:
-                C.conv1x16(xs, _pack2(pack_w1x, w), _pad_bias(b, 16), None, a, ks, 1 | 4)
-            elif kind == "1in":
-                C.conv16_fwd_x3(xs[0], xs[1], _pack2(lambda t: pack_w16_planes(ij_in_weights(t)), w),
-                                _pad_bias(b, 16), None, a[0], a[1], ks, 1)
-            else:
-                C.conv16_fwd_x3(h[0], h[1], _pack2(pack_w16, w), _pad_bias(b, 16), None, a[0], a[1], ks, 1)
-            if "nc_act" in _X3_DROP:
-                a[1].zero_()
-            saved.append(a)
-            h = a
-        z = h                                                      # [2V, I, J, K, L] fp32 (ReLU'd)
-        y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=dev)
-        C.combine_fwd(z.reshape(-1), y, R, Cc)
-        ctx.kinds, ctx.channels, ctx.dims, ctx.fast1x = kinds, channels, (V, I, J, K, L), fast
-        ctx.save_for_backward(z, *params, *saved)
-        return y.reshape(V, 1, I, J, K, L)
-
-    @staticmethod
-    def backward(ctx, gy):
-        C = _ext.ext()
-        kinds, channels = ctx.kinds, ctx.channels
-        nl = len(kinds)
-        z, *rest = ctx.saved_tensors
-        params, saved = rest[:2 * nl], rest[2 * nl:]
-        ws = _x3_weights([_std(w) for w in params[0::2]], backward=True)
-        V, I, J, K, L = ctx.dims
-        R, Cc = I * J, K * L
-        shp = tuple(z.shape)
-        dev = z.device
-        g = torch.empty((2,) + shp, dtype=torch.bfloat16, device=dev)   # d/d(last pre-activation), hi / lo
-        C.combine_bwd(gy.reshape(V, R, Cc).float().contiguous(), z, g[0], R, Cc, g[1])
-        xs = saved[0]
-        acts = saved[1:]                                              # per hidden layer: [2, 2V, ..., 16]
-        dws, dbs = [None] * nl, [None] * nl
-        gx = None
-        main = side = None
-        if _config.RUNTIME.bwd_overlap and z.is_cuda:
-            main = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-        for li in range(nl - 1, -1, -1):
-            if "nc_grad" in _X3_DROP:
-                g[1].zero_()
-            kind, w = kinds[li], ws[li]
-            ks = w.shape[-1]
-            cout = channels[li]
-            cin = 1 if li == 0 else channels[li - 1]
-            xin = xs if li == 0 else acts[li - 1]                     # [2, (G,) 2V, ..., 16]
-            gs = None
-            if ctx.fast1x and kind in ("1in", "1out"):
-                gn = _x3_fast1x_layer(C, ctx, li, kind, w, xin, g, dws, dbs, main, side, shp, ks, cin, cout)
-                if li == 0:
-                    if ctx.needs_input_grad[0]:
-                        wt = transpose_for_dgrad(w)
-                        gx = (conv_layer(g[0:1], _wsplit(wt)[0], cout, 1, relu=False)
-                              + conv_layer(g[0:1], _wsplit(wt)[1], cout, 1, relu=False)
-                              + conv_layer(g[1:2], _wsplit(wt)[0], cout, 1, relu=False))
-                    break
-                g = gn
-                continue
-            if kind == "1out":
-                gs = torch.empty((2, ij_groups(ks)) + shp + (16,), dtype=torch.bfloat16, device=dev)
-                C.ijpack(g[0], gs[0], ks, -1)
-                C.ijpack(g[1], gs[1], ks, -1)
-            # the three (X, G) products; the bias gradient is sum(G_hi) + sum(G_lo)
-            if kind == "1out":
-                combos = [(xin[0:1], g[0], gs[0]), (xin[0:1], g[1], gs[1]), (xin[1:2], g[0], gs[0])]
-            elif kind == "1in":
-                combos = [(xin[0], g[0:1], None), (xin[0], g[1:2], None), (xin[1], g[0:1], None)]
-            else:
-                combos = [(xin[0:1], g[0:1], None), (xin[0:1], g[1:2], None), (xin[1:2], g[0:1], None)]
-            on_side = li > 0
-            with _OnSide(main if on_side else None, side if on_side else None,
-                         tuple(t for t in (xin, g, gs) if t is not None)):
-                res = [_layer_wgrad(C, kind, xi, gi, gsi, ks, cin, cout) for xi, gi, gsi in combos]
-                dws[li] = ref.conv4d_weight_from_std(res[0][0] + res[1][0] + res[2][0])
-                dbs[li] = res[0][1] + res[1][1]
-            if li == 0:
-                if ctx.needs_input_grad[0]:
-                    wt = transpose_for_dgrad(w)
-                    gx = (conv_layer(g[0:1], _wsplit(wt)[0], cout, 1, relu=False)
-                          + conv_layer(g[0:1], _wsplit(wt)[1], cout, 1, relu=False)
-                          + conv_layer(g[1:2], _wsplit(wt)[0], cout, 1, relu=False))
-                break
-            gn = torch.empty((2,) + shp + (16,), dtype=torch.bfloat16, device=dev)
-            if kind == "1out":
-                wp2 = _pack2(lambda t: pack_w16_planes(plane_dgrad_weights(ij_out_weights(t))), w)
-                C.conv16_fwd_x3(gs[0], gs[1], wp2, None, xin[0], gn[0], gn[1], ks, 2)
-            else:
-                C.conv16_fwd_x3(g[0], g[1], _pack2(pack_w16, transpose_for_dgrad(w)), None, xin[0], gn[0], gn[1],
-                                ks, 2)
-            g = gn
-        if side is not None:
-            _join_side(main, side)
-            for t in dws + dbs:
-                t.record_stream(main)
-        if gx is not None:
-            gx = gx[:V] + gx[V:].permute(0, 3, 4, 1, 2)
-            gx = gx.reshape(V, 1, I, J, K, L)
-        grads = []
-        for dw, db in zip(dws, dbs):
-            grads += [dw, db]
-        return (gx, None, None, *grads)
-
-
-class NeighConsensusMixedFn(torch.autograd.Function):
-    """nc_precision='mixed' training NeighConsensus: the bf16x3 forward of
-    NeighConsensusX3FusedFn (fp32-accurate input, weights and hidden
-    activations) with a bf16 backward -- bf16 gradients, bf16 weights in the
-    data gradients, each weight gradient the (X_hi, G) + (X_lo, G) products --
-    on the bf16 training kernels (the padded-plane 1-channel path).  It keeps
-    the fp32-accurate forward for ~2/3 of the fp32 mode's NeighConsensus work.
-    Over 24 seeds (scripts/precision_ablation.py, profiles/r5/ablation) bf16,
-    this mix and fp32 took off at the same rate within noise (the earlier
-    4-seed 0.533 vs 0.535 PCK comparison is withdrawn): there is no evidence
-    that it learns where bf16 does not."""
-
-    @staticmethod
-    def forward(ctx, x, kinds, channels, *params):
-        y = NeighConsensusX3FusedFn.forward(ctx, x, kinds, channels, *params)
-        ctx.nparams = len(params)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        if not ctx.fast1x:
-            return NeighConsensusX3FusedFn.backward(ctx, gy)
-        C = _ext.ext()
-        kinds, channels = ctx.kinds, ctx.channels
-        nl = len(kinds)
-        z, *rest = ctx.saved_tensors
-        params, saved = rest[:2 * nl], rest[2 * nl:]
-        ws = list(params[0::2])
-        V, I, J, K, L = ctx.dims
-        R, Cc = I * J, K * L
-        gz = torch.empty(z.numel(), dtype=torch.bfloat16, device=z.device)
-        C.combine_bwd(gy.reshape(V, R, Cc).float().contiguous(), z, gz, R, Cc)
-        xs, acts = saved[0], saved[1:]
-        hi = [xs[0]] + [a[0:1] for a in acts]
-        lo = [xs[1]] + [a[1:2] for a in acts]
-        need_dx0 = ctx.needs_input_grad[0]
-        dws, dbs, g0 = _stack_bwd(gz.reshape(tuple(z.shape)), hi, ws, kinds, channels, need_dx0, True,
-                                  _stack_packs(ws, kinds), saved_lo=lo)
-        gx = None
-        if need_dx0:
-            g0 = g0.reshape(-1)
-            ga, gbt = g0[:V * R * Cc], g0[V * R * Cc:]
-            gb = _swap_flat(gbt.reshape(V, Cc, R), (K, L, I, J))
-            gx = (ga.reshape(V, R, Cc) + gb).reshape(V, 1, I, J, K, L)
-        grads = []
-        for dw, db in zip(dws, dbs):
-            grads += [dw, db]
-        return (gx, None, None, *grads)
-
-
-# ---------------------------------------------------------------------------
-# fp8 inference path (BASELINE config 5): OCP e4m3 activations and weights on
-# the fp8 MFMA conv kernel, ij encoding for the 1-channel layers.
-
-FP8 = torch.float8_e4m3fn
-
-
-def _fp8_weights(packed_bf16: torch.Tensor):
-    """Packed bf16 fragments -> (fp8 fragments scaled into the e4m3 range, 1/scale)."""
-    amax = float(packed_bf16.abs().max())
-    e = 0 if amax == 0 else int(np.floor(np.log2(240.0 / amax)))
-    e = max(-8, min(12, e))
-    return (packed_bf16.float() * 2.0 ** e).to(FP8), 2.0 ** -e
-
-
-# weight tensor -> {kind: (version, shape, (fp8 fragments, 1/scale))}.  Keyed by
-# the tensor OBJECT (entries die with it), never by its address: a new weight
-# tensor the caching allocator places where a freed one lived must not inherit
-# its fp8 weights.
-_FP8_W_CACHE = _weak.WeakIdKeyDictionary()
-_FP8_PINS: list | None = None
-
-
-class pin_fp8_weights:
-    """Collects every cached fp8 weight tensor used inside the block (returned
-    by ``__enter__``): a HIP graph captured there replays those exact buffers,
-    so its owner keeps them alive for as long as the graph exists
-    (eval/inloc.py PairMatcher)."""
-
-    def __enter__(self):
-        global _FP8_PINS
-        self._prev, _FP8_PINS = _FP8_PINS, []
-        return _FP8_PINS
-
-    def __exit__(self, *exc):
-        global _FP8_PINS
-        _FP8_PINS = self._prev
-        return False
-
-
-def _fp8_weights_of(w_ref: torch.Tensor, kind: str):
-    """Quantised fp8 fragments of one layer's weights, cached per weight tensor
-    and version: the amax -> scale step reads the max on the host, which must
-    not happen per pair (it serialises the stream and is illegal inside the
-    InLoc PairMatcher HIP-graph capture).  Pass the weight Parameter itself
-    (``Conv4d.weight`` with ``pre_permuted_filters=True``, the default) for the
-    cache to hit across calls; a fresh tensor per call is re-quantised."""
-    per = _FP8_W_CACHE.get(w_ref)
-    if per is None:
-        per = _FP8_W_CACHE[w_ref] = {}
-    ent = per.get(kind)
-    ver = 0 if w_ref.is_inference() else w_ref._version      # inference tensors are immutable
-    if ent is None or ent[0] != ver or ent[1] != tuple(w_ref.shape):
-        w = _std(w_ref)
-        packed = {"1in": lambda: pack_w16_planes(ij_in_weights(w)), "16": lambda: pack_w16(w),
-                  "1out": lambda: pack_w16_planes(ij_out_weights(w))}[kind]()
-        ent = per[kind] = (ver, tuple(w_ref.shape), _fp8_weights(packed))
-    if _FP8_PINS is not None:
-        _FP8_PINS.append(ent[2][0])
-    return ent[2]
-
-
-def _stack_fwd_fp8(x0: torch.Tensor, ws, bs, kinds) -> torch.Tensor:
-    """x0 [V,I,J,K,L] bf16 -> last layer output fp32 [V,I,J,K,L] (ReLU'd), fp8 inside."""
-    C = _ext.ext()
-    V, I, J, K, L = x0.shape
-    h = x0
-    for li, (w_ref, b, kind) in enumerate(zip(ws, bs, kinds)):
-        ks = w_ref.shape[0]
-        wq, osc = _fp8_weights_of(w_ref, kind)
-        if kind == "1in":
-            G = ij_groups(ks)
-            xs = torch.empty((G, V, I, J, K, L, 16), dtype=FP8, device=x0.device)
-            C.ijpack(h, xs, ks, 1)
-            y = torch.empty((V, I, J, K, L, 16), dtype=FP8, device=x0.device)
-            C.conv16f8_fwd(xs, wq, _pad_bias(b, 16), y, ks, 1, osc)
-        elif kind == "16":
-            y = torch.empty((V, I, J, K, L, 16), dtype=FP8, device=x0.device)
-            C.conv16f8_fwd(h, wq, _pad_bias(b, 16), y, ks, 1, osc)
-        else:  # "1out"
-            G, nq = ij_groups(ks), ks * ks
-            z = torch.empty((nq, V, I, J, K, L), dtype=torch.float32, device=x0.device)
-            hx = h.unsqueeze(0)
-            for gi in range(G):
-                C.conv16f8_fwd(hx, wq[gi:gi + 1], None, z[16 * gi:min(nq, 16 * gi + 16)], ks, 4, osc)
-            y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x0.device)
-            C.ijsum(z, _pad_bias(b, 1), y, ks, 1, 1)
-            del z
-            if li != len(kinds) - 1:
-                raise RuntimeError("fp8 NC path: the 1-channel output layer must be last")
-        h = y
-    return h
-
-
-def neigh_consensus_fp8(x: torch.Tensor, weights, biases, kinds, symmetric: bool = True) -> torch.Tensor:
-    """Inference-only NeighConsensus with fp8 operands (no autograd)."""
-    V, _, I, J, K, L = x.shape
-    R, Cc = I * J, K * L
-    xb = x.reshape(V, I, J, K, L).to(torch.bfloat16).contiguous()
-    if not symmetric:
-        return _stack_fwd_fp8(xb, weights, biases, kinds).reshape(V, 1, I, J, K, L)
-    xt = _swap_flat(xb.reshape(V, R, Cc), (I, J, K, L)).reshape(V, K, L, I, J)
-    if (I, J) == (K, L):
-        z = _stack_fwd_fp8(torch.cat((xb, xt), 0), weights, biases, kinds)
-    else:
-        z = torch.cat((_stack_fwd_fp8(xb, weights, biases, kinds).reshape(-1),
-                       _stack_fwd_fp8(xt, weights, biases, kinds).reshape(-1)))
-    y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x.device)
-    _ext.ext().combine_fwd(z, y, R, Cc)
-    return y.reshape(V, 1, I, J, K, L)
-
-
-# ---------------------------------------------------------------------------
-# Fused InLoc NC (csrc/nc_fused.hip): kernel sizes (3, 3), channels (<=16, 1),
-# inference.  The hidden activation stays in LDS; HBM sees the input and the
-# output volume once.  NCNET_NC_FUSED=0 falls back to the layer-by-layer path.
-_FUSED_LDS = 80 * 1024          # two workgroups per CU (160 KB LDS)
-
-
-def _cdiv(a: int, b: int) -> int:
-    return -(-a // b)
-
-
-@functools.lru_cache(maxsize=64)
-def fused_tiles(V: int, I: int, J: int, K: int, L: int):
-    """(TK, TL, R, IR) of nc_fused_k3: a (k, l) tile within the kernel's limits
-    ((TK+2)(TL+2) <= 512, TK*TL <= 384, (TK+4)(TL+4) <= 512) minimising the
-    padded layer-1 + layer-2 work, then R output planes per workgroup (as many
-    as the LDS ring allows) and row segments of IR rows until the grid has
-    ~2 workgroups per CU."""
-    best = None
-    for tk in range(1, min(K, 28) + 1):
-        for tl in range(1, min(L, 28) + 1):
-            if (tk + 2) * (tl + 2) > 512 or tk * tl > 384 or (tk + 4) * (tl + 4) > 512:
-                continue
-            n = _cdiv(K, tk) * _cdiv(L, tl)
-            cost = n * (_cdiv((tk + 2) * (tl + 2), 16) + _cdiv(tk * tl, 16))
-            if best is None or cost < best[0]:
-                best = (cost, tk, tl)
-    _, tk, tl = best
-    fixed = (tk + 4) * (tl + 10) * 32 + (tk + 2) * (tl + 8) * 32 + 2 * 5 * 64 * 16 + 268   # + ring trash / alignment
-    rps = tk * tl + (16 - (tk * tl) % 32) % 32        # ring plane stride (csrc/nc_fused.hip ncf_ring_stride)
-    r_max = max(1, (_FUSED_LDS - fixed) // (12 * rps))
-    base = V * _cdiv(K, tk) * _cdiv(L, tl)
-
-    def nwg(r, ir):
-        return base * _cdiv(J, r) * _cdiv(I, ir)
-
-    # the kernel is latency-bound (two barriers per hidden plane): prefer >= ~500
-    # workgroups (two per CU), first by splitting rows (halo (IR+2)/IR), then
-    # planes ((R+2)/R).  Measured at 3200 px: 500 workgroups (R=10, IR=75)
-    # 4.3 ms vs 6.4 ms for 1000 (IR=37); at 1600 px R=4, IR=5 0.55 ms.
-    R, IR = min(J, r_max), I
-    while nwg(R, IR) < 500 and IR > 5:
-        IR = max(5, IR // 2)
-    while nwg(R, IR) < 500 and R > 4:
-        R -= 1
-    return tk, tl, R, IR
-
-
-def _fused_weights(weights, biases, dtype=torch.bfloat16):
-    """Packed fused-kernel weights in the operand dtype (bf16, or float16 for the
-    IEEE-half kernel of half_precision models)."""
-    w1, w2 = _std(weights[0]), _std(weights[1])
-    W1p = pack_w16_planes(ij_in_weights(w1), dtype)[0].contiguous()
-    # layer-2 MFMA rows: row 4 * dj + di <- ij combo di * 3 + dj (nc_fused.hip: a
-    # lane's four rows then share dj and one output plane); other rows zero
-    wo = ij_out_weights(w2)
-    wr = torch.zeros_like(wo)
-    for di in range(3):
-        for dj in range(3):
-            wr[:, 4 * dj + di] = wo[:, 3 * di + dj]
-    W2p = pack_w16_planes(wr, dtype)[0].contiguous()
-    return W1p, _pad_bias(biases[0], 16), W2p, _pad_bias(biases[1], 1)
-
-
-def _run_fused(xb: torch.Tensor, wts) -> torch.Tensor:
-    V, I, J, K, L = xb.shape
-    y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=xb.device)
-    tk, tl, R, IR = fused_tiles(V, I, J, K, L)
-    _ext.ext().nc_fused_k3(xb, *wts, y, R, IR, tk, tl)
-    return y
-
-
-def neigh_consensus_fused_x2(x2: torch.Tensor, weights, biases) -> torch.Tensor:
-    """Symmetric fused NC on a prepared [2V, I, J, K, L] bf16 / float16 input (x,
-    then its A<->B swap: ops/mutual.py mutual_matching_nc_input) -> [V, 1, I, J, K, L] fp32."""
-    V2, I, J, K, L = x2.shape
-    V = V2 // 2
-    z = _run_fused(x2, _fused_weights(weights, biases, x2.dtype))
-    y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x2.device)
-    _ext.ext().combine_fwd(z, y, I * J, K * L)
-    return y.reshape(V, 1, I, J, K, L)
-
-
-# fused fp8 kernel (csrc/nc_fused.hip nc_fused_k3_f8_kernel): x0 (in [0, 1]
-# after MutualMatching) enters e4m3 times this power of two
-FP8_NC_X_SCALE = 256.0
-
-
-def _pow2_scale(bound: float, target: float) -> float:
-    """2^e with bound * 2^e <= target (e clamped to [-10, 12]); 1 for bound 0."""
-    if not bound > 0:
-        return 1.0
-    return 2.0 ** max(-10, min(12, int(np.floor(np.log2(target / bound)))))
-
-
-def _mx_frags(dense: torch.Tensor):
-    """[16 rows, 9 taps, 16 ch] -> (A fragments of taps 0-7 for
-    v_mfma_scale_f32_16x16x128_f8f6f4: [64 lanes, 32] with lane fr + 16 fq
-    holding row fr, taps 2fq, 2fq + 1; tap-8 fragments for
-    v_mfma_f32_16x16x32_fp8_fp8: [64, 8], lane groups fq = 0, 1 channels
-    0-7 / 8-15, fq = 2, 3 zero)."""
-    a = dense[:, :8, :].reshape(16, 4, 32).permute(1, 0, 2).reshape(64, 32)
-    b = dense.new_zeros((4, 16, 8))
-    b[:2] = dense[:, 8, :].reshape(16, 2, 8).permute(1, 0, 2)
-    return a.contiguous(), b.reshape(64, 8).contiguous()
-
-
-def _fused_weights_f8_build(weights, biases):
-    w1, w2 = _std(weights[0]).float(), _std(weights[1]).float()
-    d1 = ij_in_weights(w1)[0].reshape(16, 16, 9).permute(0, 2, 1)          # [hidden co, tap, combo]
-    wo = ij_out_weights(w2)
-    wr = torch.zeros_like(wo)
-    for di in range(3):
-        for dj in range(3):
-            wr[:, 4 * dj + di] = wo[:, 3 * di + dj]                        # layer-2 rows 4 dj + di
-    d2 = wr[0].reshape(16, 16, 9).permute(0, 2, 1)                         # [combo row, tap, hidden ci]
-    b1, b2 = _pad_bias(biases[0], 16), _pad_bias(biases[1], 1)
-    sw1 = _pow2_scale(float(d1.abs().max()), 240.0)
-    sw2 = _pow2_scale(float(d2.abs().max()), 240.0)
-    # hidden bound: x0 <= 1, so h[co] <= sum |W1[co]| + max(b1[co], 0)
-    hb = float((d1.abs().sum((1, 2)) + b1.clamp(min=0)).max())
-    sh = _pow2_scale(hb, 440.0)
-    sx = FP8_NC_X_SCALE
-    w1a, w1b = _mx_frags(d1 * sw1)
-    w2a, w2b = _mx_frags(d2 * sw2)
-    tens = tuple(t.to(FP8) for t in (w1a, w1b)) + (b1,) + tuple(t.to(FP8) for t in (w2a, w2b)) + (b2,)
-    return tens, (sx, 1.0 / (sw1 * sx), sh, 1.0 / (sw2 * sh))
-
-
-_F8_FUSED_CACHE = _weak.WeakIdKeyDictionary()
-
-
-def _fused_weights_f8(weights, biases):
-    """Quantised fused-kernel operands, cached per layer-1 weight tensor and the
-    versions of all four parameters (the amax / bound reads are host syncs,
-    illegal inside the InLoc pair-graph capture)."""
-    def ver(t):
-        return 0 if t.is_inference() else t._version
-    key = tuple((ver(t), tuple(t.shape)) for t in (*weights, *biases))
-    ent = _F8_FUSED_CACHE.get(weights[0])
-    if ent is None or ent[0] != key or ent[1] is not weights[1]:
-        ent = _F8_FUSED_CACHE[weights[0]] = (key, weights[1], _fused_weights_f8_build(weights, biases))
-    if _FP8_PINS is not None:
-        _FP8_PINS.extend(ent[2][0])
-    return ent[2]
-
-
-def neigh_consensus_fused_x2_fp8(x2: torch.Tensor, weights, biases) -> torch.Tensor:
-    """Symmetric fused NC on e4m3 operands (nc_fused_k3_f8) on a prepared
-    [2V, I, J, K, L] bf16 input -> [V, 1, I, J, K, L] fp32."""
-    V2, I, J, K, L = x2.shape
-    V = V2 // 2
-    tens, scales = _fused_weights_f8(weights, biases)
-    z = torch.empty((V2, I, J, K, L), dtype=torch.float32, device=x2.device)
-    tk, tl, R, IR = fused_tiles(V2, I, J, K, L)
-    _ext.ext().nc_fused_k3_f8(x2, *tens, z, R, IR, tk, tl, *scales)
-    y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x2.device)
-    _ext.ext().combine_fwd(z, y, I * J, K * L)
-    return y.reshape(V, 1, I, J, K, L)
-
-
-def fused_f8_applies(x: torch.Tensor, weights, channels, fp8: bool) -> bool:
-    """Would the fp8 fused kernel run this (symmetric, square) input?"""
-    return x.is_cuda and select_path(x, weights, channels, True, fp8) == "fused_fp8"
-
-
-def fused_applies(x: torch.Tensor, weights, channels, fp8: bool = False, precision: str = "bf16") -> bool:
-    """Would ``neigh_consensus`` run this input on the fused (bf16 / half) kernel?"""
-    return x.is_cuda and select_path(x, weights, channels, True, fp8, precision) == "fused"
-
-
-def neigh_consensus_fused(x: torch.Tensor, weights, biases, symmetric: bool = True) -> torch.Tensor:
-    """Inference NeighConsensus of a (3, 3) / (<=16, 1) stack on the fused kernel."""
-    V, _, I, J, K, L = x.shape
-    R, Cc = I * J, K * L
-    wts = _fused_weights(weights, biases)
-    if symmetric and (I, J) == (K, L):
-        # both branches in one launch: the cast and the transpose write straight
-        # into the halves of one [2V, ...] input (no concatenation pass)
-        x2 = torch.empty((2 * V, I, J, K, L), dtype=torch.bfloat16, device=x.device)
-        x2[:V].copy_(x.reshape(V, I, J, K, L))
-        _ext.ext().transpose(x2[:V].reshape(V, R, Cc), x2[V:].reshape(V, Cc, R))
-        z = _run_fused(x2, wts)
-        y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x.device)
-        _ext.ext().combine_fwd(z, y, R, Cc)
-        return y.reshape(V, 1, I, J, K, L)
-    xb = x.reshape(V, I, J, K, L).to(torch.bfloat16).contiguous()
-    if not symmetric:
-        return _run_fused(xb, wts).reshape(V, 1, I, J, K, L)
-    xt = _swap_flat(xb.reshape(V, R, Cc), (I, J, K, L)).reshape(V, K, L, I, J)
-    z = torch.cat((_run_fused(xb, wts).reshape(-1), _run_fused(xt, wts).reshape(-1)))
-    y = torch.empty((V, I, J, K, L), dtype=torch.float32, device=x.device)
-    _ext.ext().combine_fwd(z, y, R, Cc)
-    return y.reshape(V, 1, I, J, K, L)
+from .nc.fp8 import neigh_consensus_fp8, pin_fp8_weights
+from .nc.fused import neigh_consensus_fused, neigh_consensus_fused_x2, neigh_consensus_fused_x2_fp8
+from .nc.layers import interleave, layer_kinds, swap_pair
+from .nc.train import NeighConsensusFn, NeighConsensusPaddedFn, fast1x_ok
+from .nc.x3 import (X3_STAGES, NeighConsensusMixedFn, NeighConsensusX3Fn, NeighConsensusX3FusedFn, neigh_consensus_x3,
+                    x3_ablation, x3_dropped, x3_fused_ok)
+
+__all__ = ["neigh_consensus", "select_path", "layer_kinds", "fast1x_ok", "fp8_ok", "X3_STAGES", "x3_ablation", "x3_dropped",
+           "x3_fused_ok", "pin_fp8_weights", "neigh_consensus_x3", "neigh_consensus_fp8", "neigh_consensus_fused",
+           "neigh_consensus_fused_x2", "neigh_consensus_fused_x2_fp8", "NeighConsensusFn", "NeighConsensusPaddedFn",
+           "NeighConsensusX3Fn", "NeighConsensusX3FusedFn", "NeighConsensusMixedFn"]
+
+# Layer-level names that tests and scripts written against the one-file module
+# import from here; new code imports them from the module that defines them.
+# Functions and constants only: a name that is rebound at run time
+# (train.FAST1X, fp8._FP8_PINS, x3._X3_DROP) has no copy here, and replacing one
+# of these functions here does not change what the paths call (they resolve
+# their helpers, e.g. pack_w1x, in their own modules).
+from .nc.fused import FP8_NC_X_SCALE, _fused_weights, _fused_weights_f8_build, _pow2_scale, fused_tiles  # noqa: E402,F401
+from .nc.layers import (_nitems, _reduce_wgrad16, blocks_to_ncl, planar_to_blocks, reduce_partials,  # noqa: E402,F401
+                        wgrad16_partials, wgrad_groups, wgrad_plane_groups, wgrad_v3_groups, wgrad_v3_ok)
+from .nc.train import _stack_bwd, _stack_fwd, pack_w1x  # noqa: E402,F401
 
 
 def _fused_ok(kinds, kernel_sizes, channels, x) -> bool:
@@ -1793,41 +138,36 @@ def neigh_consensus(x: torch.Tensor, weights, biases, channels, symmetric: bool 
     instead of padding x itself)."""
     path = select_path(x, weights, channels, symmetric, fp8, precision, padded)
     kernel_sizes = [w.shape[0] for w in weights]
-    kinds = layer_kinds(channels, kernel_sizes)
-    params = []
-    for w, b in zip(weights, biases):
-        params += [w, b]
-    xf = x.float().contiguous()
+    if path in ("reference", "torch_fallback"):
+        if path == "torch_fallback":
+            _ext.torch_fallback(f"NeighConsensus kernel sizes {kernel_sizes}")
+        return ref.neigh_consensus(x.float(), [w.float() for w in weights], [b.float() for b in biases], symmetric)
     if path in ("x3_inference", "mixed", "x3_fused", "x3"):
         _ext.count("nc_x3")
     if path == "x3_inference":
         return neigh_consensus_x3(x, weights, biases, channels, symmetric)
-    if path == "mixed":
-        _ext.count("nc_mixed")
-        return NeighConsensusMixedFn.apply(xf, tuple(kinds), tuple(channels), *params)
-    if path == "x3_fused":
-        _ext.count("nc_x3_fused")
-        return NeighConsensusX3FusedFn.apply(xf, tuple(kinds), tuple(channels), *params)
-    if path == "x3":
-        return NeighConsensusX3Fn.apply(xf, symmetric, tuple(kinds), tuple(channels), *params)
     if path == "fused_fp8":
         _ext.count("nc_fused_k3_f8")
-        V, _, I, J, K, L = x.shape
-        x2 = torch.empty((2 * V, I, J, K, L), dtype=torch.bfloat16, device=x.device)
-        x2[:V].copy_(x.reshape(V, I, J, K, L))
-        _ext.ext().transpose(x2[:V].reshape(V, I * J, K * L), x2[V:].reshape(V, K * L, I * J))
-        return neigh_consensus_fused_x2_fp8(x2, weights, biases)
+        return neigh_consensus_fused_x2_fp8(swap_pair(x), weights, biases)
+    # every other path takes the input as fp32, contiguous
+    xf = x.float().contiguous()
     if path == "fused":
         _ext.count("nc_fused_k3")
         return neigh_consensus_fused(xf, weights, biases, symmetric)
+    kinds = tuple(layer_kinds(channels, kernel_sizes))
     if path == "fp8":
         _ext.count("nc_fp8")
         return neigh_consensus_fp8(xf, weights, biases, kinds, symmetric)
-    if path in ("bf16", "bf16_padded"):
-        _ext.count("nc_bf16")
-        if path == "bf16_padded":
-            return NeighConsensusPaddedFn.apply(xf, padded, symmetric, tuple(kinds), tuple(channels), *params)
-        return NeighConsensusFn.apply(xf, symmetric, tuple(kinds), tuple(channels), *params)
-    if path == "torch_fallback":
-        _ext.torch_fallback(f"NeighConsensus kernel sizes {kernel_sizes}")
-    return ref.neigh_consensus(x.float(), [w.float() for w in weights], [b.float() for b in biases], symmetric)
+    params = interleave(weights, biases)
+    if path == "mixed":
+        _ext.count("nc_mixed")
+        return NeighConsensusMixedFn.apply(xf, kinds, tuple(channels), *params)
+    if path == "x3_fused":
+        _ext.count("nc_x3_fused")
+        return NeighConsensusX3FusedFn.apply(xf, kinds, tuple(channels), *params)
+    if path == "x3":
+        return NeighConsensusX3Fn.apply(xf, symmetric, kinds, tuple(channels), *params)
+    _ext.count("nc_bf16")
+    if path == "bf16_padded":
+        return NeighConsensusPaddedFn.apply(xf, padded, symmetric, kinds, tuple(channels), *params)
+    return NeighConsensusFn.apply(xf, symmetric, kinds, tuple(channels), *params)

@@ -11,7 +11,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from ncnet_amd.ops import _ext  # noqa: E402
 from ncnet_amd.ops import reference as ref  # noqa: E402
 
-nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+nc = importlib.import_module("ncnet_amd.ops.nc.fused")
 DEV = "cuda"
 
 

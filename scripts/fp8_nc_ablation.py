@@ -27,7 +27,7 @@ from ncnet_amd.data.datasets import synthetic_correspondence_batch  # noqa: E402
 from ncnet_amd.engine.reference_impl import ReferenceAlgorithm  # noqa: E402
 from ncnet_amd.models import ImMatchNet  # noqa: E402
 from ncnet_amd.ops import reference as ref  # noqa: E402
-from ncnet_amd.ops.neigh_consensus import FP8_NC_X_SCALE, _pow2_scale  # noqa: E402
+from ncnet_amd.ops.nc.fused import FP8_NC_X_SCALE, _pow2_scale  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from precision_agreement import agreement  # noqa: E402

@@ -17,7 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ncnet_amd.ops import _ext  # noqa: E402
-from ncnet_amd.ops.neigh_consensus import wgrad_groups, wgrad_plane_groups, wgrad_v3_groups  # noqa: E402
+from ncnet_amd.ops.nc.layers import wgrad_groups, wgrad_plane_groups, wgrad_v3_groups  # noqa: E402
 from ncnet_amd.ops.packing import ij_groups, ij_in_weights, ij_out_weights, pack_w16, pack_w16_planes  # noqa: E402
 
 

@@ -1,7 +1,7 @@
 """Fused InLoc NC (csrc/nc_fused.hip) at the 3200 px volume [2, 75, 100, 75,
 100]: time the kernel for several (R planes per workgroup, IR rows per
 workgroup) choices, incl. the one-16-wave-workgroup-per-CU variant (LDS > 80
-KB), on one box, interleaved.  Diagnostic for ops/neigh_consensus.py
+KB), on one box, interleaved.  Diagnostic for ops/nc/fused.py
 fused_tiles."""
 import importlib
 import os
@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from ncnet_amd.ops import _ext  # noqa: E402
 from ncnet_amd.ops import reference as ref  # noqa: E402
 
-nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+nc = importlib.import_module("ncnet_amd.ops.nc.fused")
 dev = "cuda"
 g = torch.Generator(device=dev).manual_seed(5)
 x2 = torch.rand((2, 75, 100, 75, 100), device=dev, generator=g).to(torch.bfloat16)

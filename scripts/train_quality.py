@@ -203,7 +203,7 @@ def main(argv=None):
                     help="the reference run's compute dtype (bf16 / fp16: autocast; fp16 with loss scaling)")
     ap.add_argument("--x3-drop", type=str, default="",
                     help="with --nc-precision fp32: comma list of bf16x3 stages run in plain bf16 "
-                         "(ops/neigh_consensus.py X3_STAGES: corr, nc_in, nc_w, nc_act, nc_grad)")
+                         "(ops/nc/x3.py X3_STAGES: corr, nc_in, nc_w, nc_act, nc_grad)")
     ap.add_argument("--no-ref", action="store_true", help="skip the fp32 reference run (ablations)")
     ap.add_argument("--fp32-trunk", choices=["", "x3", "miopen"], default="",
                     help="the fp32 trunk's implementation (default: the mode's own)")

@@ -210,7 +210,7 @@ def transpose(x, y):
 
 
 class EmuExt:
-    """Namespace with the binding names used by ops/neigh_consensus.py and ops/conv4d.py."""
+    """Namespace with the binding names used by ops/nc/ and ops/conv4d.py."""
     conv16_fwd = staticmethod(conv16_fwd)
     conv16_blk_fwd = staticmethod(conv16_blk_fwd)
     conv16_fwd_x3 = staticmethod(conv16_fwd_x3)

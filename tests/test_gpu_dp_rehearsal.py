@@ -2,7 +2,7 @@
 ranks per device, so the collectives run over gloo; the driver's 2/4/8-GPU
 runs use RCCL, one GPU per rank).  Two ranks train the headline model
 (ResNet-101 + NC 5,5,5 / 16,16,1, 400 px: the compile-time fast kernels, the
-side-stream weight gradients of ops/neigh_consensus.py and the trunk
+side-stream weight gradients of ops/nc/train.py and the trunk
 prefetch) through the real Trainer -- flat gradient bucket all-reduce, FlatAdam
 with the 1/world average folded in -- and must end bit-identical to each other
 and equal to ONE process doing FlatAdam on the mean of the two shards'

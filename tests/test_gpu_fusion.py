@@ -158,7 +158,7 @@ def test_reduce_cols_matches_torch_layouts():
     bitwise equal."""
     import importlib
     from ncnet_amd.ops import reference as ref
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.layers")
     torch.manual_seed(1)
     ks = 5
     p16 = torch.randn(204, ks * ks, ks * ks, 16, 16, device=DEV)

@@ -127,7 +127,7 @@ def test_wgrad16v4_other_planes(ks, T, tune):
     """wgrad16v4 at the other compile-time planes vs the general wgrad16v3 and
     the fp64 weight gradient.  (5, 30): 34-voxel X rows, two DMA instructions
     per row -- wgrad16v3 cannot stage them, so only the fp64 check applies."""
-    from ncnet_amd.ops.neigh_consensus import wgrad16_partials, _reduce_wgrad16
+    from ncnet_amd.ops.nc.layers import wgrad16_partials, _reduce_wgrad16
     torch.manual_seed(9)
     V, I, J = 2, 6, 9
     x = torch.randn(V, I, J, T, T, 16, device=DEV).to(torch.bfloat16)
@@ -457,7 +457,7 @@ def test_wgrad16_kernel(variant, ks, shape):
     offset; multi-tile K, L exercise the per-item halo), full and plane-only
     modes, vs autograd of the fp64 oracle."""
     import importlib
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.layers")
     C = _ext.ext()
     torch.manual_seed(11)
     V, I, J, K, L = shape
@@ -490,7 +490,7 @@ def test_wgrad16_kernel(variant, ks, shape):
 def test_wgrad16v3_priority_flag(flags, monkeypatch, tune):
     """wgrad16v3 with the waves-4..7 s_setprio tuning bit: same sums as the oracle."""
     import importlib
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.layers")
     tune("wgrad_flags", flags)
     torch.manual_seed(12)
     V, I, J, K, L, ks = 2, 6, 5, 25, 25, 5
@@ -968,7 +968,7 @@ def test_nc_fused_k3_vs_quantized_oracle(cfg):
     production choice, fused_tiles)."""
     import importlib
     from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
     torch.manual_seed(21)
     V, I, J, K, L = 2, 9, 13, 11, 14
     w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
@@ -1056,7 +1056,7 @@ def test_nc_fused_k3_one_wide_workgroup():
     quantized fp64 oracle."""
     import importlib
     from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
     torch.manual_seed(23)
     V, I, J, K, L = 1, 6, 26, 17, 22
     w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
@@ -1082,7 +1082,7 @@ def test_nc_fused_k3_last_volume_borders(tiles):
     large error at the I/J borders)."""
     import importlib
     from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
     torch.manual_seed(29)
     I, J, K, L = 7, 9, 11, 13
     n = I * J * K * L
@@ -1138,7 +1138,7 @@ def test_nc_fused_k3_f8_vs_quantized_oracle(cfg):
     cfg = (R, IR, TK, TL); the 3200 px (15 x 20, R 10) and 1600 px (19 x 17,
     R 8) tiles are the compile-time instantiations."""
     import importlib
-    nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
     torch.manual_seed(41)
     V, I, J, K, L = 2, 9, 13, 11, 14
     w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
@@ -1262,6 +1262,7 @@ def test_neigh_consensus_fast1x_matches_ij_path(monkeypatch, symmetric):
     gradient."""
     import importlib
     nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc_train = importlib.import_module("ncnet_amd.ops.nc.train")    # defines (and reads) FAST1X
     torch.manual_seed(31)
     x = torch.rand(2, 1, 25, 25, 25, 25, device=DEV).to(torch.bfloat16).float()
     ws, bs, cin = [], [], 1
@@ -1272,7 +1273,7 @@ def test_neigh_consensus_fast1x_matches_ij_path(monkeypatch, symmetric):
     g = torch.randn(2, 1, 25, 25, 25, 25, device=DEV)
     outs = {}
     for fast in (True, False):
-        monkeypatch.setattr(nc, "FAST1X", fast)
+        monkeypatch.setattr(nc_train, "FAST1X", fast)
         xx = x.clone().requires_grad_(True)
         pw = [w.clone().requires_grad_(True) for w in ws]
         pb = [b.clone().requires_grad_(True) for b in bs]
@@ -1310,6 +1311,7 @@ def _fast1x_vs_quantized_oracle(symmetric, perturb=None, seed=31, ks=(5, 5, 5), 
     import importlib
     from ncnet_amd.engine import quantized_oracle as qo
     nc = importlib.import_module("ncnet_amd.ops.neigh_consensus")
+    nc_train = importlib.import_module("ncnet_amd.ops.nc.train")    # where _stack_fwd / _stack_packs resolve pack_w1x
     gen = torch.Generator(device=DEV).manual_seed(seed)
 
     def ints(shape, lo, hi, scale):
@@ -1328,7 +1330,7 @@ def _fast1x_vs_quantized_oracle(symmetric, perturb=None, seed=31, ks=(5, 5, 5), 
     pb = [b.clone().requires_grad_(True) for b in bs]
     kinds = nc.layer_kinds(list(ch), list(ks))
     assert nc.fast1x_ok(kinds, list(ch), list(ks), xx, symmetric)
-    orig = nc.pack_w1x
+    orig = nc_train.pack_w1x
     if perturb is not None:
         calls = []
 
@@ -1338,12 +1340,12 @@ def _fast1x_vs_quantized_oracle(symmetric, perturb=None, seed=31, ks=(5, 5, 5), 
                 p = perturb(p)
             calls.append(1)
             return p
-        nc.pack_w1x = mutated
+        nc_train.pack_w1x = mutated
     try:
         y = nc.neigh_consensus(xx, pw, pb, list(ch), symmetric=symmetric)
         (y * g).sum().backward()
     finally:
-        nc.pack_w1x = orig
+        nc_train.pack_w1x = orig
     got = [y.detach(), xx.grad] + [p.grad for p in pw + pb]
     xr = x.double().requires_grad_(True)
     wr = [ref.conv4d_weight_to_std(w.double()).requires_grad_(True) for w in ws]

@@ -8,7 +8,8 @@ import torch
 
 from ncnet_amd.ops import _ext
 from ncnet_amd.ops import reference as ref
-from ncnet_amd.ops.neigh_consensus import _stack_bwd, _stack_fwd, blocks_to_ncl, layer_kinds, planar_to_blocks
+from ncnet_amd.ops.nc.layers import blocks_to_ncl, layer_kinds, planar_to_blocks
+from ncnet_amd.ops.nc.train import _stack_bwd, _stack_fwd
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

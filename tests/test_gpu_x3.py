@@ -1,5 +1,5 @@
 """GPU: the fused bf16x3 ("fp32-accurate") training NeighConsensus
-(ops/neigh_consensus.py NeighConsensusX3FusedFn on csrc/conv4d_fwd.hip EPI_X3)
+(ops/nc/x3.py NeighConsensusX3FusedFn on csrc/conv4d_fwd.hip EPI_X3)
 against autograd of the fp64 reference algorithm.  25 x 25 planes run the
 conv16v4 kernel with the three phases, smaller planes the conv16v2 ones."""
 import pytest

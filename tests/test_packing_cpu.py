@@ -52,12 +52,12 @@ def test_packed_weights_plan_matches_packers(ks, shared):
 
 
 def test_reduce_partials_layouts_cpu():
-    """ops/neigh_consensus.reduce_partials (the CPU path of the reduce_cols
+    """ops/nc/layers.py reduce_partials (the CPU path of the reduce_cols
     launch): the scatter map built from the layout function reproduces
     layout(part.sum(0)) for the three weight-gradient layouts of the training
     stack, slices included."""
     from ncnet_amd.ops import reference as ref
-    from ncnet_amd.ops.neigh_consensus import _reduce_wgrad16, reduce_partials
+    from ncnet_amd.ops.nc.layers import _reduce_wgrad16, reduce_partials
     torch.manual_seed(0)
     ks = 5
     p16 = torch.randn(6, ks * ks, ks * ks, 16, 16)
