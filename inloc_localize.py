@@ -26,6 +26,12 @@ PV, ht_top10_NC4D_PV_localization.m:44); results do not depend on the worker
 count.  --cache_dir keeps one file per pair (parfor_NC4D_PE_pnponly.m:4-6
 skips pairs whose .mat exists), so an interrupted run resumes.
 
+--pnp_device gpu moves the RANSAC itself to the GPU (ncnet_amd/eval/
+localization_gpu.py, csrc/pnp.hip): the workers still load the cutouts and
+build the tentatives, the parent alone opens the device and solves all pairs
+of --pnp_chunk queries with one batched launch.  Its results are cached apart
+from the numpy path's (pnp_gpu/...), whose cache keys do not change.
+
 Inputs on disk (InLoc layout): --cutout_dir/<dbname>.mat with 'XYZcut'
 [H,W,3]; optional --trans_dir/<dbname>.txt holding the 4x4 (or 3x4)
 scan-to-global matrix.  --synthetic N builds a fake scene to smoke-test the
@@ -45,6 +51,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ncnet_amd.eval.inloc import load_shortlist  # noqa: E402
 from ncnet_amd.eval.localization import (DEFAULT_THRESHOLDS, evaluate_queries, localization_rate,  # noqa: E402
                                          p3p_ransac, tentative_correspondences)
+from ncnet_amd.eval import localization_gpu  # noqa: E402
 from ncnet_amd.eval import pose_verification as pv  # noqa: E402
 
 
@@ -110,6 +117,32 @@ def _cache_load(cpath, key):
     return z
 
 
+def _pnp_tentatives(q, jj, dbname, m, q_size, cfg):
+    """The pair's tentatives: (rays [3, n], X [3, n], the pair's generator), or
+    None without matches or without the cutout's XYZ map."""
+    xyz_path = os.path.join(cfg["cutout_dir"], dbname + ".mat")
+    if m is None or not os.path.exists(xyz_path):
+        return None
+    xyz = _loadmat(xyz_path)["XYZcut"].astype(np.float64)
+    P_after = None
+    if cfg["trans_dir"]:
+        tp = os.path.join(cfg["trans_dir"], dbname + ".txt")
+        if os.path.exists(tp):
+            P_after = np.loadtxt(tp)
+    rng = _pair_rng(cfg["seed"], q, jj)
+    rays, X, _, _ = tentative_correspondences(m, cfg["thr"], q_size, xyz, cfg["focal"], P_after,
+                                              cfg["n_subsample"], rng)
+    return rays, X, rng
+
+
+def _cache_store(cpath, key, P, n_inl):
+    if cpath:
+        os.makedirs(os.path.dirname(cpath), exist_ok=True)
+        tmp = cpath + ".tmp.npz"
+        np.savez(tmp, P=np.full((3, 4), np.nan) if P is None else P, n_inliers=n_inl, key=key)
+        os.replace(tmp, cpath)
+
+
 def _pnp_pair(task):
     """One (query, cutout) pair: threshold, tentatives, P3P LO-RANSAC
     (parfor_NC4D_PE_pnponly.m).  Cached on disk when cache_dir is set."""
@@ -121,31 +154,45 @@ def _pnp_pair(task):
         P = z["P"]
         return q, jj, dbname, (None if np.isnan(P).all() else P), int(z["n_inliers"])
     P, n_inl = None, 0
-    xyz_path = os.path.join(cfg["cutout_dir"], dbname + ".mat")
-    if m is not None and os.path.exists(xyz_path):
-        xyz = _loadmat(xyz_path)["XYZcut"].astype(np.float64)
-        P_after = None
-        if cfg["trans_dir"]:
-            tp = os.path.join(cfg["trans_dir"], dbname + ".txt")
-            if os.path.exists(tp):
-                P_after = np.loadtxt(tp)
-        rng = _pair_rng(cfg["seed"], q, jj)
-        rays, X, _, _ = tentative_correspondences(m, cfg["thr"], q_size, xyz, cfg["focal"], P_after,
-                                                  cfg["n_subsample"], rng)
+    tent = _pnp_tentatives(q, jj, dbname, m, q_size, cfg)
+    if tent is not None:
+        rays, X, rng = tent
         if rays.shape[1] >= 3:
             P, inl = p3p_ransac(rays, X, np.radians(cfg["pnp_thr"]), cfg["ransac_iters"], rng=rng)
             n_inl = int(inl.sum())
-    if cpath:
-        os.makedirs(os.path.dirname(cpath), exist_ok=True)
-        tmp = cpath + ".tmp.npz"
-        np.savez(tmp, P=np.full((3, 4), np.nan) if P is None else P, n_inliers=n_inl, key=key)
-        os.replace(tmp, cpath)
+    _cache_store(cpath, key, P, n_inl)
     return q, jj, dbname, P, n_inl
+
+
+def _pnp_gpu_cache(task):
+    """Cache file and key of a pair's batched-GPU result: a directory and a key
+    of their own, so the numpy path's cache is neither read nor overwritten."""
+    q, jj, qname, dbname, m, q_size, cfg = task
+    if not cfg["cache_dir"]:
+        return None, ""
+    return (_cache_path(cfg["cache_dir"], qname, dbname, "pnp_gpu"),
+            _cache_key(cfg, _PNP_KEYS, m, extra=(tuple(q_size), q, jj, "pnp_device=gpu")))
+
+
+def _pnp_prepare(task):
+    """Worker half of --pnp_device gpu: the cached result of the pair, or its
+    tentatives for the parent's batched RANSAC.  Never touches the GPU.
+    -> (q, jj, dbname, done, P, n_inliers, rays, X)."""
+    q, jj, qname, dbname, m, q_size, cfg = task
+    cpath, key = _pnp_gpu_cache(task)
+    z = _cache_load(cpath, key)
+    if z is not None:
+        P = z["P"]
+        return q, jj, dbname, True, (None if np.isnan(P).all() else P), int(z["n_inliers"]), None, None
+    tent = _pnp_tentatives(q, jj, dbname, m, q_size, cfg)
+    if tent is None:
+        return q, jj, dbname, False, None, 0, np.zeros((3, 0)), np.zeros((3, 0))
+    return q, jj, dbname, False, None, 0, tent[0], tent[1]
 
 
 def _cfg(args) -> dict:
     return {k: getattr(args, k) for k in ("cutout_dir", "trans_dir", "thr", "focal", "n_subsample", "pnp_thr",
-                                          "ransac_iters", "seed", "cache_dir", "query_dir", "pv_device")}
+                                          "ransac_iters", "seed", "cache_dir", "query_dir", "pv_device", "pnp_device")}
 
 
 def localize_query(q_matches: np.ndarray, db_names, q_size, args, q: int = 0, qname: str = "query"):
@@ -187,7 +234,9 @@ def localize_all(jobs, args):
             m = mats[0, jj] if jj < mats.shape[1] else None
             tasks.append((q, jj, qname, dbname, m, q_size, cfg))
     res = {q: [None] * min(len(names), args.pnp_topN) for q, _, _, names in jobs}
-    if args.workers > 1 and len(tasks) > 1:
+    if cfg["pnp_device"] == "gpu":
+        outs = _localize_tasks_gpu(tasks, args, cfg)
+    elif args.workers > 1 and len(tasks) > 1:
         with _executor(args.workers) as ex:
             outs = list(ex.map(_pnp_pair, tasks, chunksize=max(1, len(tasks) // (4 * args.workers))))
     else:
@@ -195,6 +244,44 @@ def localize_all(jobs, args):
     for q, jj, dbname, P, n in outs:
         res[q][jj] = (dbname, P, n)
     return res
+
+
+def _localize_tasks_gpu(tasks, args, cfg):
+    """--pnp_device gpu: the workers build the tentatives of a chunk of queries,
+    the parent solves all of the chunk's pairs with one batched launch (keys
+    from (seed, q, jj), as _pair_rng) and writes the cache."""
+    chunks, cur, seen = [], [], set()
+    for t in tasks:                                    # tasks are grouped by query
+        if t[0] not in seen and len(seen) and len(seen) % max(1, args.pnp_chunk) == 0:
+            chunks.append(cur)
+            cur = []
+        seen.add(t[0])
+        cur.append(t)
+    if cur:
+        chunks.append(cur)
+    ex = _executor(args.workers) if args.workers > 1 and len(tasks) > 1 else None
+    outs = []
+    try:
+        for chunk in chunks:
+            if ex is not None:
+                prep = list(ex.map(_pnp_prepare, chunk, chunksize=max(1, len(chunk) // (4 * args.workers))))
+            else:
+                prep = [_pnp_prepare(t) for t in chunk]
+            todo = [i for i, p in enumerate(prep) if not p[3]]
+            solved = localization_gpu.p3p_ransac_batch(
+                [(prep[i][6], prep[i][7]) for i in todo], np.radians(cfg["pnp_thr"]), cfg["ransac_iters"],
+                keys=[[cfg["seed"], prep[i][0], prep[i][1]] for i in todo], device="gpu") if todo else []
+            got = dict(zip(todo, solved))
+            for i, (q, jj, dbname, done, P, n_inl, _, _) in enumerate(prep):
+                if not done:
+                    P, inl = got[i]
+                    n_inl = int(inl.sum()) if P is not None else 0
+                    _cache_store(*_pnp_gpu_cache(chunk[i]), P, n_inl)
+                outs.append((q, jj, dbname, P, n_inl))
+    finally:
+        if ex is not None:
+            ex.shutdown()
+    return outs
 
 
 def _texture(Xw: np.ndarray) -> np.ndarray:
@@ -353,6 +440,10 @@ def main(argv=None):
     ap.add_argument("--pnp_thr", type=float, default=0.2, help="angular inlier threshold (degrees)")
     ap.add_argument("--n_subsample", type=int, default=None)
     ap.add_argument("--ransac_iters", type=int, default=10000)
+    ap.add_argument("--pnp_device", choices=["cpu", "gpu"], default="cpu",
+                    help="cpu: numpy P3P LO-RANSAC per pair on the workers; gpu: all pairs of --pnp_chunk queries "
+                         "in one batched HIP launch from the parent")
+    ap.add_argument("--pnp_chunk", type=int, default=64, help="queries per batched GPU RANSAC call")
     ap.add_argument("--rerank", choices=["none", "inliers"], default="none")
     ap.add_argument("--refposes", type=str, default="")
     ap.add_argument("--name", type=str, default="NCNet")

@@ -63,6 +63,9 @@ int ncnet_adam_masked(float*, float*, float*, float*, long long, const int*, con
 int ncnet_adam_finalize(float*, int*, int*, hipStream_t);
 int ncnet_resize_norm_u8(const void*, const long long*, float*, int, int, int, const float*, const float*, hipStream_t);
 int ncnet_debug_selftest(int*, hipStream_t);
+int ncnet_p3p_solve(const double*, const double*, int, double*, int*, hipStream_t);
+int ncnet_p3p_ransac_batch(const double*, const double*, const int*, const long long*, int, long long, double, int, double,
+                           int, double*, int*, uint8_t*, int*, int*, hipStream_t);
 int ncnet_pad_geom(int, int, int, int*, int*);
 int ncnet_pad_planes(const void*, int, void*, int, int, int, int, int, int, int, hipStream_t);
 int ncnet_conv1x16(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, long long, long long, hipStream_t);
@@ -1016,6 +1019,75 @@ void resize_norm_u8(Tensor src, Tensor meta, Tensor out, std::vector<double> mea
      "resize_norm_u8");
 }
 
+// Minimal P3P solver (csrc/pnp.hip), test entry point: rays / X [M, 3, 3] fp64
+// (row k = k-th bearing vector / world point) -> (P [M, 4, 3, 4] with the valid
+// poses first and NaN after them, nsol [M] int32).
+std::vector<Tensor> p3p_solve(Tensor rays, Tensor X) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(rays.device());
+  check(rays, "rays", at::kDouble); check(X, "X", at::kDouble);
+  TORCH_CHECK(rays.dim() == 3 && rays.size(1) == 3 && rays.size(2) == 3, "rays must be [M, 3, 3]");
+  check_shape(X, "X", rays.sizes().vec());
+  TORCH_CHECK(X.device() == rays.device(), "rays and X must be on one device");
+  const int64_t M = rays.size(0);
+  TORCH_CHECK(M < (1ll << 28), "too many triplets");
+  Tensor P = torch::empty({M, 4, 3, 4}, rays.options());
+  Tensor nsol = torch::empty({M}, rays.options().dtype(at::kInt));
+  ok(ncnet_p3p_solve((const double*)rays.data_ptr(), (const double*)X.data_ptr(), (int)M, (double*)P.data_ptr(),
+                     (int*)nsol.data_ptr(), cur_stream(rays)),
+     "p3p_solve");
+  return {P, nsol};
+}
+
+// Batched P3P LO-RANSAC (csrc/pnp.hip).  rays / X [N, 3] fp64: the tentatives of B
+// problems, problem b owns rows offsets[b]:offsets[b+1]; offsets [B + 1] int32,
+// keys [B] int64 (all on the GPU).  Returns (P [B, 3, 4] fp64, NaN without a pose;
+// n_inliers [B] int32; inlier_mask [N] uint8).  rounds: optional [B] int32 that
+// receives the number of sampling rounds each problem ran.
+std::vector<Tensor> p3p_ransac_batch(Tensor rays, Tensor X, Tensor offsets, Tensor keys, double thr_rad,
+                                     int64_t max_iters, double confidence, int64_t lo_iters,
+                                     c10::optional<Tensor> rounds) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(rays.device());
+  check(rays, "rays", at::kDouble); check(X, "X", at::kDouble);
+  check(offsets, "offsets", at::kInt); check(keys, "keys", at::kLong);
+  TORCH_CHECK(rays.dim() == 2 && rays.size(1) == 3, "rays must be [N, 3]");
+  check_shape(X, "X", rays.sizes().vec());
+  TORCH_CHECK(offsets.dim() == 1 && offsets.size(0) >= 1, "offsets must be [B + 1]");
+  const int64_t N = rays.size(0), B = offsets.size(0) - 1;
+  check_shape(keys, "keys", {B});
+  TORCH_CHECK(X.device() == rays.device() && offsets.device() == rays.device() && keys.device() == rays.device(),
+              "rays, X, offsets and keys must be on one device");
+  TORCH_CHECK(N < (1ll << 31), "too many tentatives for int32 offsets");
+  TORCH_CHECK(thr_rad > 0.0 && thr_rad < 1.5707963267948966, "thr_rad must be in (0, pi / 2)");
+  TORCH_CHECK(max_iters >= 0 && max_iters < (1ll << 31), "max_iters must be in [0, 2^31)");
+  TORCH_CHECK(lo_iters >= 0 && lo_iters <= 65536, "lo_iters must be in [0, 65536]");
+  TORCH_CHECK(confidence >= 0.0 && confidence <= 1.0, "confidence must be in [0, 1]");
+  {
+    // the kernel forms addresses from offsets: they must be monotone and end at N
+    Tensor oc = offsets.cpu();
+    const int* o = (const int*)oc.data_ptr();
+    TORCH_CHECK(o[0] == 0, "offsets[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) TORCH_CHECK(o[b + 1] >= o[b], "offsets must be non-decreasing (at ", b + 1, ")");
+    TORCH_CHECK(o[B] == N, "offsets[B] = ", o[B], " must equal N = ", N);
+  }
+  int* rptr = nullptr;
+  if (rounds.has_value() && rounds->defined()) {
+    check(*rounds, "rounds", at::kInt);
+    check_shape(*rounds, "rounds", {B});
+    TORCH_CHECK(rounds->device() == rays.device(), "rounds must be on the device of rays");
+    rptr = (int*)rounds->data_ptr();
+  }
+  Tensor P = torch::full({B, 3, 4}, std::numeric_limits<double>::quiet_NaN(), rays.options());
+  Tensor ninl = torch::zeros({B}, rays.options().dtype(at::kInt));
+  Tensor mask = torch::zeros({N}, rays.options().dtype(at::kByte));
+  Tensor list = torch::empty({N}, rays.options().dtype(at::kInt));
+  ok(ncnet_p3p_ransac_batch((const double*)rays.data_ptr(), (const double*)X.data_ptr(), (const int*)offsets.data_ptr(),
+                            (const long long*)keys.data_ptr(), (int)B, (long long)N, std::cos(thr_rad), (int)max_iters,
+                            confidence, (int)lo_iters, (double*)P.data_ptr(), (int*)ninl.data_ptr(),
+                            (uint8_t*)mask.data_ptr(), (int*)list.data_ptr(), rptr, cur_stream(rays)),
+     "p3p_ransac_batch");
+  return {P, ninl, mask};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 HIP kernels for ncnet_amd";
   m.def("conv16_fwd", &conv16_fwd);
@@ -1068,6 +1140,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nc_fused_k3_f8", &nc_fused_k3_f8);
   m.def("resize_norm_u8", &resize_norm_u8);
   m.def("debug_selftest", &debug_selftest);
+  m.def("p3p_solve", &p3p_solve);
+  m.def("p3p_ransac_batch", &p3p_ransac_batch, py::arg("rays"), py::arg("X"), py::arg("offsets"), py::arg("keys"),
+        py::arg("thr_rad"), py::arg("max_iters"), py::arg("confidence"), py::arg("lo_iters"),
+        py::arg("rounds") = py::none());
   m.def("nonfinite_count", &nonfinite_count);
   m.def("adam_masked", &adam_masked);
   m.def("adam_finalize", &adam_finalize);
