@@ -32,6 +32,12 @@ build the tentatives, the parent alone opens the device and solves all pairs
 of --pnp_chunk queries with one batched launch.  Its results are cached apart
 from the numpy path's (pnp_gpu/...), whose cache keys do not change.
 
+--pv_device gpu does the same for dense pose verification (ncnet_amd/eval/
+pose_verification_gpu.py, csrc/pv.hip): the parent loads each scan once (a
+loader thread reads the next one meanwhile) and scores all its candidates with
+one batched call; its cache is pv_gpu/..., the pv/... files and keys of the
+torch path do not change.
+
 Inputs on disk (InLoc layout): --cutout_dir/<dbname>.mat with 'XYZcut'
 [H,W,3]; optional --trans_dir/<dbname>.txt holding the 4x4 (or 3x4)
 scan-to-global matrix.  --synthetic N builds a fake scene to smoke-test the
@@ -53,6 +59,7 @@ from ncnet_amd.eval.localization import (DEFAULT_THRESHOLDS, evaluate_queries, l
                                          p3p_ransac, tentative_correspondences)
 from ncnet_amd.eval import localization_gpu  # noqa: E402
 from ncnet_amd.eval import pose_verification as pv  # noqa: E402
+from ncnet_amd.eval import pose_verification_gpu  # noqa: E402
 
 
 def _loadmat(path):
@@ -384,10 +391,7 @@ def _pv_scan(task):
             todo.append((q, jj, qname, dbname, P, cpath, key))
     if not todo:
         return out
-    scan = None
-    if os.path.exists(scan_path):
-        P_after = pv.load_transformation(trans_path) if os.path.exists(trans_path) else None
-        scan = pv.load_scan(scan_path, P_after)
+    scan = _pv_load_scan(scan_path, trans_path)
     qimgs = {}
     for q, jj, qname, dbname, P, cpath, key in todo:
         qpath = os.path.join(cfg["query_dir"], qname)
@@ -396,12 +400,72 @@ def _pv_scan(task):
             if qname not in qimgs:
                 qimgs[qname] = np.asarray(Image.open(qpath).convert("RGB"))
             s = float(pv.pv_score(qimgs[qname], scan[0], scan[1], P, cfg["focal"], device=cfg["pv_device"])[0])
-        if cpath:
-            os.makedirs(os.path.dirname(cpath), exist_ok=True)
-            tmp = cpath + ".tmp.npz"
-            np.savez(tmp, score=s, key=key)
-            os.replace(tmp, cpath)
+        _pv_store(cpath, key, s)
         out.append((q, jj, s))
+    return out
+
+
+def _pv_store(cpath, key, s):
+    if cpath:
+        os.makedirs(os.path.dirname(cpath), exist_ok=True)
+        tmp = cpath + ".tmp.npz"
+        np.savez(tmp, score=s, key=key)
+        os.replace(tmp, cpath)
+
+
+def _pv_load_scan(scan_path, trans_path):
+    if not os.path.exists(scan_path):
+        return None
+    P_after = pv.load_transformation(trans_path) if os.path.exists(trans_path) else None
+    return pv.load_scan(scan_path, P_after)
+
+
+def _verify_tasks_gpu(tasks):
+    """--pv_device gpu: runs in the parent only, which alone opens the device.
+    Per scan, every uncached candidate goes to one batched call
+    (pose_verification_gpu.pv_scores_batch); one loader thread reads the next
+    scan meanwhile.  The cache lives in pv_gpu/... under a key of its own, so the
+    torch path's pv/... files are neither read nor overwritten."""
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    out, work = [], []
+    for scan_path, trans_path, items, cfg in tasks:
+        todo = []
+        for q, jj, qname, dbname, P in items:
+            cpath = _cache_path(cfg["cache_dir"], qname, dbname, "pv_gpu") if cfg["cache_dir"] else None
+            key = _cache_key(cfg, ("focal",), P, extra=(os.path.basename(scan_path), "pv_device=gpu")) if cpath else ""
+            z = _cache_load(cpath, key)
+            if z is not None:
+                out.append((q, jj, float(z["score"])))
+            else:
+                todo.append((q, jj, qname, P, cpath, key))
+        if todo:
+            work.append((scan_path, trans_path, todo, cfg))
+    if not work:
+        return out
+    qimgs = {}
+    with ThreadPoolExecutor(max_workers=1) as loader:
+        nxt = loader.submit(_pv_load_scan, work[0][0], work[0][1])
+        for n, (scan_path, trans_path, todo, cfg) in enumerate(work):
+            scan = nxt.result()
+            if n + 1 < len(work):
+                nxt = loader.submit(_pv_load_scan, work[n + 1][0], work[n + 1][1])
+            scores = [0.0] * len(todo)
+            batch = []
+            for i, (q, jj, qname, P, cpath, key) in enumerate(todo):
+                qpath = os.path.join(cfg["query_dir"], qname)
+                if scan is not None and P is not None and os.path.exists(qpath):
+                    if qname not in qimgs:
+                        qimgs[qname] = np.asarray(Image.open(qpath).convert("RGB"))
+                    batch.append(i)
+            if batch:
+                got = pose_verification_gpu.pv_scores_batch([qimgs[todo[i][2]] for i in batch], scan[0], scan[1],
+                                                            [todo[i][3] for i in batch], cfg["focal"], device="gpu")
+                for i, s in zip(batch, got):
+                    scores[i] = float(s)
+            for (q, jj, qname, P, cpath, key), s in zip(todo, scores):
+                _pv_store(cpath, key, s)
+                out.append((q, jj, s))
     return out
 
 
@@ -416,7 +480,9 @@ def verify_all(results, qnames, args):
             scan_path, trans_path = pv.scan_paths(dbname, args.scan_dir, args.scan_suffix)
             groups.setdefault((scan_path, trans_path), []).append((q, jj, qnames[q], dbname, P))
     tasks = [(sp, tp, items, cfg) for (sp, tp), items in sorted(groups.items())]
-    if args.workers > 1 and len(tasks) > 1 and args.pv_device == "cpu":
+    if args.pv_device == "gpu":
+        outs = _verify_tasks_gpu(tasks)
+    elif args.workers > 1 and len(tasks) > 1 and args.pv_device == "cpu":
         with _executor(args.workers) as ex:
             outs = [o for part in ex.map(_pv_scan, tasks) for o in part]
     else:
@@ -453,7 +519,9 @@ def main(argv=None):
     ap.add_argument("--scan_dir", type=str, default="datasets/inloc/scans")
     ap.add_argument("--scan_suffix", type=str, default=".ptx.mat")
     ap.add_argument("--query_dir", type=str, default="datasets/inloc/query/iphone7")
-    ap.add_argument("--pv_device", type=str, default="cpu")
+    ap.add_argument("--pv_device", type=str, default="cpu",
+                    help="cpu, or a torch device string: pv_score per candidate; gpu: all candidates of a scan in one "
+                         "batched call from the parent (csrc/pv.hip)")
     ap.add_argument("--plot", type=str, default="", help="write the localization curves to this image")
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--seed", type=int, default=0)

@@ -66,6 +66,10 @@ int ncnet_debug_selftest(int*, hipStream_t);
 int ncnet_p3p_solve(const double*, const double*, int, double*, int*, hipStream_t);
 int ncnet_p3p_ransac_batch(const double*, const double*, const int*, const long long*, int, long long, double, int, double,
                            int, double*, int*, uint8_t*, int*, int*, hipStream_t);
+int ncnet_pv_pmax();
+int ncnet_pv_render(const double*, const float*, long long, const double*, int, int, int, unsigned long long*, int*, float*,
+                    uint8_t*, hipStream_t);
+int ncnet_pv_desc_err(const float*, const float*, const uint8_t*, int, int, int, int, int, float*, hipStream_t);
 int ncnet_pad_geom(int, int, int, int*, int*);
 int ncnet_pad_planes(const void*, int, void*, int, int, int, int, int, int, int, hipStream_t);
 int ncnet_conv1x16(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, long long, long long, hipStream_t);
@@ -1088,6 +1092,62 @@ std::vector<Tensor> p3p_ransac_batch(Tensor rays, Tensor X, Tensor offsets, Tens
   return {P, ninl, mask};
 }
 
+// Batched z-buffer renderer (csrc/pv.hip): one scan, xyz [N, 3] fp64 and rgb [N, 3]
+// fp32, through C poses KP [C, 3, 4] fp64 onto h x w targets.  Returns
+// (synth [C, h, w, 3] fp32, NaN where no point lands; flag [C, h, w] bool;
+// winner [C, h, w] int32, the index of each pixel's point or -1).  Launches of at
+// most PV_PMAX poses are looped here.
+std::vector<Tensor> pv_render(Tensor xyz, Tensor rgb, Tensor KP, int64_t h, int64_t w) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(xyz.device());
+  check(xyz, "xyz", at::kDouble); check(rgb, "rgb", at::kFloat); check(KP, "KP", at::kDouble);
+  TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3, "xyz must be [N, 3]");
+  check_shape(rgb, "rgb", xyz.sizes().vec());
+  TORCH_CHECK(KP.dim() == 3 && KP.size(1) == 3 && KP.size(2) == 4, "KP must be [C, 3, 4]");
+  TORCH_CHECK(rgb.device() == xyz.device() && KP.device() == xyz.device(), "xyz, rgb and KP must be on one device");
+  TORCH_CHECK(h >= 1 && w >= 1, "h and w must be at least 1");
+  const int64_t N = xyz.size(0), C = KP.size(0);
+  TORCH_CHECK(N < (1ll << 31), "too many points for int32 indices");
+  TORCH_CHECK(h < (1ll << 31) && w < (1ll << 31) && h * w < (1ll << 31) && C * h * w < (1ll << 31),
+              "C * h * w must be below 2^31");
+  Tensor synth = torch::empty({C, h, w, 3}, rgb.options());
+  Tensor flag = torch::empty({C, h, w}, rgb.options().dtype(at::kBool));
+  Tensor winner = torch::full({C, h, w}, -1, rgb.options().dtype(at::kInt));
+  Tensor zbuf = torch::full({C, h * w}, (int64_t)0x7FF0000000000000ll, rgb.options().dtype(at::kLong));
+  const int64_t pmax = ncnet_pv_pmax(), hw = h * w;
+  for (int64_t c0 = 0; c0 < C; c0 += pmax) {
+    const int64_t cl = std::min(pmax, C - c0);
+    ok(ncnet_pv_render((const double*)xyz.data_ptr(), (const float*)rgb.data_ptr(), (long long)N,
+                       (const double*)KP.data_ptr() + 12 * c0, (int)cl, (int)h, (int)w,
+                       (unsigned long long*)zbuf.data_ptr() + c0 * hw, (int*)winner.data_ptr() + c0 * hw,
+                       (float*)synth.data_ptr() + 3 * c0 * hw, (uint8_t*)flag.data_ptr() + c0 * hw, cur_stream(xyz)),
+       "pv_render");
+  }
+  return {synth, flag, winner};
+}
+
+// Fused dense-SIFT tail + RootSIFT + descriptor distance (csrc/pv.hip).  oq / os
+// [B, 8, H, W] fp32: the pooled orientation maps of the query side and the
+// synthetic side; flag [B, H, W] bool.  Returns err [B, ny * nx] fp32 on the
+// keypoint grid of dense_sift(size 8, step 4), NaN where flag is false.
+Tensor pv_desc_err(Tensor oq, Tensor os, Tensor flag) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(oq.device());
+  check(oq, "oq", at::kFloat); check(os, "os", at::kFloat); check(flag, "flag", at::kBool);
+  TORCH_CHECK(oq.dim() == 4 && oq.size(1) == 8, "oq must be [B, 8, H, W]");
+  check_shape(os, "os", oq.sizes().vec());
+  const int64_t B = oq.size(0), H = oq.size(2), W = oq.size(3);
+  check_shape(flag, "flag", {B, H, W});
+  TORCH_CHECK(os.device() == oq.device() && flag.device() == oq.device(), "oq, os and flag must be on one device");
+  TORCH_CHECK(H >= 1 && W >= 1, "H and W must be at least 1");
+  TORCH_CHECK(oq.numel() < (1ll << 31), "B * 8 * H * W must be below 2^31");
+  // keypoint centres 15, 19, ... while centre <= H - 16 (dense_sift: arange(2 * size - 1, H - 2 * size + 1, step))
+  const int64_t ny = H >= 31 ? (H - 27) / 4 : 0, nx = W >= 31 ? (W - 27) / 4 : 0;
+  Tensor err = torch::empty({B, ny * nx}, oq.options());
+  ok(ncnet_pv_desc_err((const float*)oq.data_ptr(), (const float*)os.data_ptr(), (const uint8_t*)flag.data_ptr(), (int)B,
+                       (int)H, (int)W, (int)ny, (int)nx, (float*)err.data_ptr(), cur_stream(oq)),
+     "pv_desc_err");
+  return err;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 HIP kernels for ncnet_amd";
   m.def("conv16_fwd", &conv16_fwd);
@@ -1144,6 +1204,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("p3p_ransac_batch", &p3p_ransac_batch, py::arg("rays"), py::arg("X"), py::arg("offsets"), py::arg("keys"),
         py::arg("thr_rad"), py::arg("max_iters"), py::arg("confidence"), py::arg("lo_iters"),
         py::arg("rounds") = py::none());
+  m.def("pv_render", &pv_render, py::arg("xyz"), py::arg("rgb"), py::arg("KP"), py::arg("h"), py::arg("w"));
+  m.def("pv_desc_err", &pv_desc_err, py::arg("oq"), py::arg("os"), py::arg("flag"));
+  m.attr("PV_PMAX") = (int64_t)ncnet_pv_pmax();   // poses per pv_render launch
   m.def("nonfinite_count", &nonfinite_count);
   m.def("adam_masked", &adam_masked);
   m.def("adam_finalize", &adam_finalize);
