@@ -142,7 +142,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, v
     bsrc = CSRC / "bindings.cpp"
     bobj = bdir / "bindings.o"
     objs.append(bobj)
-    if force or _newer(bsrc, bobj):
+    if force or _newer(bsrc, bobj, headers):           # it includes csrc/launchers.h
         cxx = ["g++", "-O2"] if variant != "asan" else [CLANGXX, "-O1", "-g", "-fsanitize=address",
                                                         "-fno-omit-frame-pointer"]
         cmd = cxx + ["-fPIC", "-std=c++17", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

@@ -8,77 +8,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <hip/hip_runtime.h>
 
-extern "C" {
-int ncnet_conv16_fwd(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, int,
-                     long long, long long, hipStream_t);
-int ncnet_set_tuning(const char*, int, int);
-int ncnet_conv16_blk_fwd(const void*, const void*, const float*, float*, int, int, int, int, int, int, int, int, long long,
-                         hipStream_t);
-int ncnet_wgrad16(const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_wgrad16p(const void*, const void*, float*, float*, int, int, int, int, int, int, int, int, int, long long,
-                   long long, hipStream_t);
-int ncnet_wgrad16v3(const void*, const void*, float*, float*, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_ijpack(const void*, int, void*, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_conv16f8_fwd(const void*, const void*, const float*, void*, int, int, int, int, int, int, int, int, int, float, hipStream_t);
-int ncnet_ijsum(const float*, const float*, float*, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_bias_act(void*, const float*, long long, int, int, int, hipStream_t);
-int ncnet_maxpool_bias_act(const void*, void*, const float*, int, int, int, int, int, int, int, int, int, int, int,
-                           hipStream_t);
-int ncnet_conv2d_nhwc_x3(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_stem_im2col_x3(const float*, void*, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_maxpool_x3(const void*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_x3_to_f32(const void*, float*, long long, int, hipStream_t);
-int ncnet_conv2d_nhwc(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_cout1_taps_fwd(const void*, const void*, const float*, float*, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_gemm_lt(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, hipStream_t);
-int ncnet_l2norm_rows(const void*, int, void*, float*, int, int, float, void*, int, hipStream_t);
-int ncnet_l2norm_rows_bwd(const float*, const float*, const float*, float*, int, int, hipStream_t);
-int ncnet_corr_gemm(const void*, const void*, void*, const int*, const int*, int, int, int, int, long long, long long,
-                    long long, int, float, int, hipStream_t);
-int ncnet_corr_gemm_pool2(const void*, const void*, float*, uint8_t*, int, int, int, int, int, int, long long, long long,
-                          float, int, hipStream_t);
-int ncnet_stats_rows(const float*, float*, int*, float*, long long, int, int, hipStream_t);
-int ncnet_stats_cols(const float*, float*, int*, float*, int, int, int, float*, int, int, hipStream_t);
-int ncnet_gather_bf16(const float*, const int*, void*, long long, long long, hipStream_t);
-int ncnet_reduce_cols(const float* const*, float* const*, const int* const*, const int*, const int*, const long long*,
-                      int, hipStream_t);
-int ncnet_stats2d(const float*, float*, int*, float*, float*, int*, float*, int, int, int, float*, int, hipStream_t);
-int ncnet_match_candidates(const float*, const float*, const int*, const float*, const float*, const int*,
-                           const uint8_t*, int, int, int, int, int, float*, float*, long long*, hipStream_t);
-int ncnet_mm_apply(const float*, const float*, const float*, float*, void*, void*, int, int, int, float, int, int, int, int,
-                   int, int, hipStream_t);
-int ncnet_mm_bwd(const float*, const float*, const float*, const int*, const float*, const int*, float*, float*, float*,
-                 int, int, int, float, float*, hipStream_t);
-int ncnet_combine_fwd(const float*, float*, int, int, int, hipStream_t);
-int ncnet_combine_bwd(const float*, const float*, void*, void*, int, int, int, hipStream_t);
-int ncnet_softmax_max_bwd(const float*, const float*, const int*, const float*, const float*, const int*, const float*,
-                          const float*, const float*, float*, int, int, int, int, float, const float*, hipStream_t);
-int ncnet_score_sum(const float*, const float*, const float*, const float*, const float*, const float*, int, int, int, int,
-                    float, float*, hipStream_t);
-int ncnet_maxpool4d(const void*, int, float*, uint8_t*, int, int, int, int, int, int, hipStream_t);
-int ncnet_transpose(const void*, void*, int, int, int, int, hipStream_t);
-int ncnet_nonfinite_count(const float*, long long, int*, hipStream_t);
-int ncnet_adam_masked(float*, float*, float*, float*, long long, const int*, const float*, float, float, float, float,
-                      float, float, hipStream_t);
-int ncnet_adam_finalize(float*, int*, int*, hipStream_t);
-int ncnet_resize_norm_u8(const void*, const long long*, float*, int, int, int, const float*, const float*, hipStream_t);
-int ncnet_debug_selftest(int*, hipStream_t);
-int ncnet_p3p_solve(const double*, const double*, int, double*, int*, hipStream_t);
-int ncnet_p3p_ransac_batch(const double*, const double*, const int*, const long long*, int, long long, double, int, double,
-                           int, double*, int*, uint8_t*, int*, int*, hipStream_t);
-int ncnet_pv_pmax();
-int ncnet_pv_render(const double*, const float*, long long, const double*, int, int, int, unsigned long long*, int*, float*,
-                    uint8_t*, hipStream_t);
-int ncnet_pv_desc_err(const float*, const float*, const uint8_t*, int, int, int, int, int, float*, hipStream_t);
-int ncnet_pad_geom(int, int, int, int*, int*);
-int ncnet_pad_planes(const void*, int, void*, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_conv1x16(const void*, const void*, const float*, const void*, void*, int, int, int, int, int, int, int, int, long long, long long, hipStream_t);
-int ncnet_wgrad1x16(const void*, const void*, float*, float*, int, int, int, int, int, int, int, hipStream_t);
-int ncnet_nc_fused_k3(const void*, const void*, const float*, const void*, const float*, float*, int, int, int, int,
-                      int, int, int, int, int, int, hipStream_t);
-int ncnet_nc_fused_k3_f8(const void*, const void*, const void*, const float*, const void*, const void*, const float*,
-                         float*, int, int, int, int, int, int, int, int, int, float, float, float, float, hipStream_t);
-}
+#include "launchers.h"
 
 namespace {
 
@@ -97,6 +27,37 @@ void check(const Tensor& t, const char* name, c10::ScalarType dt) {
 void check_shape(const Tensor& t, const char* name, std::vector<int64_t> shape) {
   TORCH_CHECK(t.sizes().vec() == shape, name, " has shape ", t.sizes(), ", expected ", c10::IntArrayRef(shape));
 }
+// an optional operand: dtype and shape when given
+void check_opt(const c10::optional<Tensor>& t, const char* name, c10::ScalarType dt, std::vector<int64_t> shape) {
+  if (t.has_value()) { check(*t, name, dt); check_shape(*t, name, std::move(shape)); }
+}
+// an optional operand this call needs
+void check_req(const c10::optional<Tensor>& t, const char* name, c10::ScalarType dt, std::vector<int64_t> shape) {
+  TORCH_CHECK(t.has_value(), "Expected ", name, ".has_value() to be true, but got false.  "
+              "(Could this error message be improved?  If so, please report an enhancement request to PyTorch.)");
+  check_opt(t, name, dt, std::move(shape));
+}
+// epilogue operands of the 16-channel Conv4d layers: epi 1 needs bias fp32 [16],
+// epi 2 the ReLU mask M, bf16 with the output volume's shape vs
+void check_epi(int64_t epi, const c10::optional<Tensor>& bias, const c10::optional<Tensor>& M,
+               const std::vector<int64_t>& vs) {
+  if (epi == 1) check_req(bias, "bias", at::kFloat, {16});
+  if (epi == 2) check_req(M, "M", at::kBFloat16, vs);
+}
+// optional 1-element fp32 bias of the Cout = 1 layers
+void check_bias1(const c10::optional<Tensor>& bias) {
+  if (bias.has_value()) { check(*bias, "bias", at::kFloat); TORCH_CHECK(bias->numel() == 1, "bias must have 1 element"); }
+}
+// X [V,I,J,K,L,16] (npg 0) or group planes [G,V,I,J,K,L,16] (npg = G); vs = [V,I,J,K,L,16]
+struct Vol16 {
+  bool grp; int64_t npg; std::vector<int64_t> vs;
+  int64_t wplanes(int64_t ks) const { return grp ? npg : ks * ks; }   // weight planes: one per group, else per (di, dj)
+};
+Vol16 vol16(const Tensor& X) {
+  const bool grp = X.dim() == 7;
+  TORCH_CHECK((X.dim() == 6 || grp) && X.size(-1) == 16, "X must be [V,I,J,K,L,16] or [G,V,I,J,K,L,16]");
+  return {grp, grp ? X.size(0) : 0, std::vector<int64_t>(X.sizes().begin() + (grp ? 1 : 0), X.sizes().end())};
+}
 void ok(int rc, const char* what) { TORCH_CHECK(rc == 0, what, " launch failed (code ", rc, ")"); }
 template <typename T>
 const T* opt_ptr(const c10::optional<Tensor>& t) { return t.has_value() && t->defined() ? (const T*)t->data_ptr() : nullptr; }
@@ -105,10 +66,6 @@ int conv_pairs16(int ks) { return (ks * ks + 1) / 2; }
 // Conv4d kernel sizes with HIP kernels: 5 and 3 (NC-Net's), 1 and 7.
 void check_ks(int64_t ks) { TORCH_CHECK(ks == 1 || ks == 3 || ks == 5 || ks == 7, "Conv4d kernel size must be 1, 3, 5 or 7 (got ", ks, ")"); }
 
-// X [V,I,J,K,L,16] (all KS*KS planes (i+di-P, j+dj-P)) or X [G,V,I,J,K,L,16]
-// (group planes: G input groups at the (i, j) plane, Wp [G, ...], in-plane taps only).
-// epi: 0 none -> bf16, 1 bias+ReLU -> bf16, 2 ReLU-mask M -> bf16,
-//      4 fp32 channel-planar [nco,V,I,J,K,L] (first nco <= 16 output channels).
 // padded 1-channel planes (csrc/conv1x.hip): {LP, PPL} of a (K, L) plane
 std::vector<int64_t> pad_geom(int64_t K, int64_t L, int64_t ks) {
   int lp, ppl;
@@ -156,8 +113,7 @@ bool conv1x16(Tensor Xp, Tensor Wa, c10::optional<Tensor> bias, c10::optional<Te
   const auto g = pad_geom(K, L, ks);
   if (x3) { check_shape(Xp, "Xp", {2, V * I * J, g[1]}); check_shape(Wa, "Wa", {2, ks * ks, 64, 8}); }
   else { check_shape(Xp, "Xp", {V * I * J, g[1]}); check_shape(Wa, "Wa", {ks * ks, 64, 8}); }
-  if (e == 1) { TORCH_CHECK(bias.has_value()); check(*bias, "bias", at::kFloat); check_shape(*bias, "bias", {16}); }
-  if (e == 2) { TORCH_CHECK(M.has_value()); check(*M, "M", at::kBFloat16); check_shape(*M, "M", {V, I, J, K, L, 16}); }
+  check_epi(e, bias, M, {V, I, J, K, L, 16});
   const int nt = ncnet_set_tuning("nt_store", 0, 0);
   const long long xlo = x3 ? (long long)V * I * J * g[1] : 0, ylo = x3 ? (long long)Y1.numel() : 0;
   const int r = ncnet_conv1x16(Xp.data_ptr(), Wa.data_ptr(), opt_ptr<float>(bias), opt_ptr<void>(M), Y.data_ptr(),
@@ -182,7 +138,7 @@ bool wgrad1x16(Tensor D, Tensor X1, Tensor part, c10::optional<Tensor> partb, in
   TORCH_CHECK(part.dim() == 4 && part.size(0) >= 1, "part must be [G, ks^2, 32, 16]");
   const int64_t G = part.size(0);
   check_shape(part, "part", {G, ks * ks, 32, 16});
-  if (partb.has_value()) { check(*partb, "partb", at::kFloat); check_shape(*partb, "partb", {G, 16}); }
+  check_opt(partb, "partb", at::kFloat, {G, 16});
   TORCH_CHECK(V * I * J < (1ll << 31), "too many planes");
   const int r = ncnet_wgrad1x16(D.data_ptr(), X1.data_ptr(), (float*)part.data_ptr(),
                                 partb.has_value() ? (float*)partb->data_ptr() : nullptr, (int)G, (int)V, (int)I,
@@ -190,33 +146,6 @@ bool wgrad1x16(Tensor D, Tensor X1, Tensor part, c10::optional<Tensor> partb, in
   TORCH_CHECK(r != -1, "wgrad1x16: no kernel instantiation for ks=", ks, " K=", K, " L=", L);
   ok(r, "wgrad1x16");
   return true;
-}
-
-void conv16_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, c10::optional<Tensor> M, Tensor Y, int64_t ks, int64_t epi) {
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  check(X, "X", at::kBFloat16); check(Wp, "Wp", at::kBFloat16);
-  check_ks(ks);
-  const bool grp = X.dim() == 7;
-  TORCH_CHECK((X.dim() == 6 || grp) && X.size(-1) == 16, "X must be [V,I,J,K,L,16] or [G,V,I,J,K,L,16]");
-  const int64_t npg = grp ? X.size(0) : 0;
-  std::vector<int64_t> vs(X.sizes().begin() + (grp ? 1 : 0), X.sizes().end());   // [V,I,J,K,L,16]
-  TORCH_CHECK(epi == 0 || epi == 1 || epi == 2 || epi == 4, "conv16_fwd: epi must be 0, 1, 2 or 4");
-  int64_t nco = 16;
-  if (epi == 4) {
-    check(Y, "Y", at::kFloat);
-    nco = Y.size(0);
-    TORCH_CHECK(nco >= 1 && nco <= 16, "planar output channels out of range");
-    check_shape(Y, "Y", {nco, vs[0], vs[1], vs[2], vs[3], vs[4]});
-  } else {
-    check(Y, "Y", at::kBFloat16);
-    check_shape(Y, "Y", vs);
-  }
-  check_shape(Wp, "Wp", {grp ? npg : ks * ks, conv_pairs16(ks), 64, 8});
-  if (epi == 1) { TORCH_CHECK(bias.has_value()); check(*bias, "bias", at::kFloat); check_shape(*bias, "bias", {16}); }
-  if (epi == 2) { TORCH_CHECK(M.has_value()); check(*M, "M", at::kBFloat16); check_shape(*M, "M", vs); }
-  ok(ncnet_conv16_fwd(X.data_ptr(), Wp.data_ptr(), opt_ptr<float>(bias), opt_ptr<void>(M), Y.data_ptr(), vs[0],
-                      vs[1], vs[2], vs[3], vs[4], ks, epi, (int)npg, (int)nco, 0, 0, cur_stream(X)),
-     "conv16_fwd");
 }
 
 // Launcher tuning switch ``name`` (common.h NcnetTuning): returns its value
@@ -236,47 +165,97 @@ static long long elem_offset(const Tensor& a, const Tensor& b) {
   return d / (long long)a.element_size();
 }
 
-// fp32-accurate ("bf16x3") Conv4d layer, KS 3 / 5:
+// Conv4d 16 -> 16 forward, the shared body of conv16_fwd and conv16_fwd_x3.
+// X [V,I,J,K,L,16] (all KS*KS planes (i+di-P, j+dj-P)) or X [G,V,I,J,K,L,16]
+// (group planes: G input groups at the (i, j) plane, Wp [G, ...], in-plane taps only).
+// epi: 0 none -> bf16, 1 bias+ReLU -> bf16, 2 ReLU-mask M -> bf16,
+//      4 fp32 channel-planar [nco,V,I,J,K,L] (first nco <= 16 output channels).
+// fp32-accurate ("bf16x3") layer (Xl, Yl given), KS 3 / 5, epi 1 or 2:
 //   y = conv(Xh, Wh) + conv(Xh, Wl) + conv(Xl, Wh)   (one kernel, fp32 accumulators)
-// X / Xl: [V,I,J,K,L,16] or group planes [G,V,I,J,K,L,16]; Wp2 [2, planes, nq, 64, 8]
-// (hi set, lo set); epi 1: y = relu(y + bias), epi 2: y = y * (M > 0) (M: the hi part of
-// the previous layer's ReLU output).  Output split: Y = bf16(y), Yl = bf16(y - Y).
+// Wp = Wp2 [2, planes, nq, 64, 8] (hi set, lo set); epi 2: M is the hi part of the
+// previous layer's ReLU output.  Output split: Y = bf16(y), Yl = bf16(y - Y).
+void conv16_fwd_body(const char* what, Tensor X, const Tensor* Xl, Tensor Wp, c10::optional<Tensor> bias,
+                     c10::optional<Tensor> M, Tensor Y, const Tensor* Yl, int64_t ks, int64_t epi) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  const bool x3 = Xl != nullptr;
+  const char* wname = x3 ? "Wp2" : "Wp";
+  check(X, "X", at::kBFloat16);
+  if (x3) check(*Xl, "Xl", at::kBFloat16);
+  check(Wp, wname, at::kBFloat16);
+  if (x3) {
+    check(Y, "Y", at::kBFloat16); check(*Yl, "Yl", at::kBFloat16);
+    TORCH_CHECK(ks == 3 || ks == 5, "conv16_fwd_x3: kernel size 3 or 5");
+  } else {
+    check_ks(ks);
+  }
+  const Vol16 v = vol16(X);
+  const auto& vs = v.vs;
+  int64_t nco = 16;
+  if (x3) {
+    TORCH_CHECK(Xl->sizes() == X.sizes(), "Xl must match X");
+    check_shape(Y, "Y", vs); check_shape(*Yl, "Yl", vs);
+    check_shape(Wp, wname, {2, v.wplanes(ks), conv_pairs16(ks), 64, 8});
+    TORCH_CHECK(epi == 1 || epi == 2, "conv16_fwd_x3: epi must be 1 or 2");
+  } else {
+    TORCH_CHECK(epi == 0 || epi == 1 || epi == 2 || epi == 4, "conv16_fwd: epi must be 0, 1, 2 or 4");
+    if (epi == 4) {
+      check(Y, "Y", at::kFloat);
+      nco = Y.size(0);
+      TORCH_CHECK(nco >= 1 && nco <= 16, "planar output channels out of range");
+      check_shape(Y, "Y", {nco, vs[0], vs[1], vs[2], vs[3], vs[4]});
+    } else {
+      check(Y, "Y", at::kBFloat16);
+      check_shape(Y, "Y", vs);
+    }
+    check_shape(Wp, wname, {v.wplanes(ks), conv_pairs16(ks), 64, 8});
+  }
+  check_epi(epi, bias, M, vs);
+  ok(ncnet_conv16_fwd(X.data_ptr(), Wp.data_ptr(), opt_ptr<float>(bias), opt_ptr<void>(M), Y.data_ptr(), vs[0], vs[1],
+                      vs[2], vs[3], vs[4], ks, x3 ? (int)epi | 64 : (int)epi, (int)v.npg, (int)nco,
+                      x3 ? elem_offset(X, *Xl) : 0, x3 ? elem_offset(Y, *Yl) : 0, cur_stream(X)),
+     what);
+}
+void conv16_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, c10::optional<Tensor> M, Tensor Y, int64_t ks,
+                int64_t epi) {
+  conv16_fwd_body("conv16_fwd", X, nullptr, Wp, bias, M, Y, nullptr, ks, epi);
+}
 void conv16_fwd_x3(Tensor X, Tensor Xl, Tensor Wp2, c10::optional<Tensor> bias, c10::optional<Tensor> M, Tensor Y,
                    Tensor Yl, int64_t ks, int64_t epi) {
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  check(X, "X", at::kBFloat16); check(Xl, "Xl", at::kBFloat16); check(Wp2, "Wp2", at::kBFloat16);
-  check(Y, "Y", at::kBFloat16); check(Yl, "Yl", at::kBFloat16);
-  TORCH_CHECK(ks == 3 || ks == 5, "conv16_fwd_x3: kernel size 3 or 5");
-  const bool grp = X.dim() == 7;
-  TORCH_CHECK((X.dim() == 6 || grp) && X.size(-1) == 16, "X must be [V,I,J,K,L,16] or [G,V,I,J,K,L,16]");
-  TORCH_CHECK(Xl.sizes() == X.sizes(), "Xl must match X");
-  const int64_t npg = grp ? X.size(0) : 0;
-  std::vector<int64_t> vs(X.sizes().begin() + (grp ? 1 : 0), X.sizes().end());
-  check_shape(Y, "Y", vs); check_shape(Yl, "Yl", vs);
-  check_shape(Wp2, "Wp2", {2, grp ? npg : ks * ks, conv_pairs16(ks), 64, 8});
-  TORCH_CHECK(epi == 1 || epi == 2, "conv16_fwd_x3: epi must be 1 or 2");
-  if (epi == 1) { TORCH_CHECK(bias.has_value()); check(*bias, "bias", at::kFloat); check_shape(*bias, "bias", {16}); }
-  if (epi == 2) { TORCH_CHECK(M.has_value()); check(*M, "M", at::kBFloat16); check_shape(*M, "M", vs); }
-  ok(ncnet_conv16_fwd(X.data_ptr(), Wp2.data_ptr(), opt_ptr<float>(bias), opt_ptr<void>(M), Y.data_ptr(), vs[0],
-                      vs[1], vs[2], vs[3], vs[4], ks, (int)epi | 64, (int)npg, 16, elem_offset(X, Xl),
-                      elem_offset(Y, Yl), cur_stream(X)),
-     "conv16_fwd_x3");
+  conv16_fwd_body("conv16_fwd_x3", X, &Xl, Wp2, bias, M, Y, &Yl, ks, epi);
 }
 
-// Cout = 1 layer (<= 16 input channels) in output-plane-block mode:
-// Y [V,I,J,K,L] fp32 = act(bias + conv); Wp [(ks+3)^2, nq, 64, 8] (packing.blk_out_weights).
-void conv16_blk_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, Tensor Y, int64_t ks, int64_t relu) {
+// Cout = 1 layer (<= 16 input channels) in output-plane-block mode, the shared body of
+// conv16_blk_fwd and conv16_blk_fwd_x3: Y [V,I,J,K,L] fp32 = act(bias + conv);
+// Wp [(ks+3)^2, nq, 64, 8] (packing.blk_out_weights).  bf16x3 (Xl given, KS 3 / 5): X / Xl hi / lo
+// input blocks, Wp = Wp2 [2, (ks+3)^2, nq, 64, 8]; Y accumulated over the three phases.
+void conv16_blk_fwd_body(const char* what, Tensor X, const Tensor* Xl, Tensor Wp, c10::optional<Tensor> bias, Tensor Y,
+                         int64_t ks, int64_t relu) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  check(X, "X", at::kBFloat16); check(Wp, "Wp", at::kBFloat16); check(Y, "Y", at::kFloat);
-  check_ks(ks);
+  const bool x3 = Xl != nullptr;
+  const char* wname = x3 ? "Wp2" : "Wp";
+  check(X, "X", at::kBFloat16);
+  if (x3) check(*Xl, "Xl", at::kBFloat16);
+  check(Wp, wname, at::kBFloat16); check(Y, "Y", at::kFloat);
+  if (x3) { TORCH_CHECK(ks == 3 || ks == 5, "conv16_blk_fwd_x3: kernel size 3 or 5"); }
+  else check_ks(ks);
   TORCH_CHECK(X.dim() == 6 && X.size(-1) == 16, "X must be [V,I,J,K,L,16]");
+  if (x3) { TORCH_CHECK(Xl->sizes() == X.sizes(), "Xl must match X"); }
   std::vector<int64_t> vs(X.sizes().begin(), X.sizes().end() - 1);
   check_shape(Y, "Y", vs);
-  check_shape(Wp, "Wp", {(ks + 3) * (ks + 3), conv_pairs16(ks), 64, 8});
-  if (bias.has_value()) { check(*bias, "bias", at::kFloat); TORCH_CHECK(bias->numel() == 1, "bias must have 1 element"); }
+  std::vector<int64_t> ws = {(ks + 3) * (ks + 3), conv_pairs16(ks), 64, 8};
+  if (x3) ws.insert(ws.begin(), 2);
+  check_shape(Wp, wname, ws);
+  check_bias1(bias);
   ok(ncnet_conv16_blk_fwd(X.data_ptr(), Wp.data_ptr(), opt_ptr<float>(bias), Y.data_ptr<float>(), vs[0], vs[1], vs[2],
-                          vs[3], vs[4], ks, (int)relu, 0, 0, cur_stream(X)),
-     "conv16_blk_fwd");
+                          vs[3], vs[4], ks, (int)relu, x3 ? 1 : 0, x3 ? elem_offset(X, *Xl) : 0, cur_stream(X)),
+     what);
+}
+void conv16_blk_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, Tensor Y, int64_t ks, int64_t relu) {
+  conv16_blk_fwd_body("conv16_blk_fwd", X, nullptr, Wp, bias, Y, ks, relu);
+}
+void conv16_blk_fwd_x3(Tensor X, Tensor Xl, Tensor Wp2, c10::optional<Tensor> bias, Tensor Y, int64_t ks,
+                       int64_t relu) {
+  conv16_blk_fwd_body("conv16_blk_fwd_x3", X, &Xl, Wp2, bias, Y, ks, relu);
 }
 
 // Cout = 1 layer with the in-plane taps as the MFMA rows (csrc/cout1.hip):
@@ -290,32 +269,13 @@ bool cout1_taps_fwd(Tensor X, Tensor Wt, c10::optional<Tensor> bias, Tensor Y, i
   std::vector<int64_t> vs(X.sizes().begin(), X.sizes().end() - 1);
   check_shape(Y, "Y", vs);
   check_shape(Wt, "Wt", {ks * ks, 64, 8});
-  if (bias.has_value()) { check(*bias, "bias", at::kFloat); TORCH_CHECK(bias->numel() == 1, "bias must have 1 element"); }
+  check_bias1(bias);
   TORCH_CHECK(vs[0] * vs[1] * vs[2] * vs[3] * vs[4] < (1LL << 40), "cout1_taps_fwd: volume too large");
   const int rc = ncnet_cout1_taps_fwd(X.data_ptr(), Wt.data_ptr(), opt_ptr<float>(bias), Y.data_ptr<float>(), vs[0],
                                       vs[1], vs[2], vs[3], vs[4], ks, (int)relu, cur_stream(X));
   if (rc == -1) return false;
   ok(rc, "cout1_taps_fwd");
   return true;
-}
-
-// bf16x3 Cout = 1 layer in output-plane-block mode: X / Xl hi / lo input blocks,
-// Wp2 [2, (ks+3)^2, nq, 64, 8]; Y fp32 = act(bias + conv) accumulated over the three phases.
-void conv16_blk_fwd_x3(Tensor X, Tensor Xl, Tensor Wp2, c10::optional<Tensor> bias, Tensor Y, int64_t ks,
-                       int64_t relu) {
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  check(X, "X", at::kBFloat16); check(Xl, "Xl", at::kBFloat16); check(Wp2, "Wp2", at::kBFloat16);
-  check(Y, "Y", at::kFloat);
-  TORCH_CHECK(ks == 3 || ks == 5, "conv16_blk_fwd_x3: kernel size 3 or 5");
-  TORCH_CHECK(X.dim() == 6 && X.size(-1) == 16, "X must be [V,I,J,K,L,16]");
-  TORCH_CHECK(Xl.sizes() == X.sizes(), "Xl must match X");
-  std::vector<int64_t> vs(X.sizes().begin(), X.sizes().end() - 1);
-  check_shape(Y, "Y", vs);
-  check_shape(Wp2, "Wp2", {2, (ks + 3) * (ks + 3), conv_pairs16(ks), 64, 8});
-  if (bias.has_value()) { check(*bias, "bias", at::kFloat); TORCH_CHECK(bias->numel() == 1, "bias must have 1 element"); }
-  ok(ncnet_conv16_blk_fwd(X.data_ptr(), Wp2.data_ptr(), opt_ptr<float>(bias), Y.data_ptr<float>(), vs[0], vs[1],
-                          vs[2], vs[3], vs[4], ks, (int)relu, 1, elem_offset(X, Xl), cur_stream(X)),
-     "conv16_blk_fwd_x3");
 }
 
 // Weight gradient partials.  mode 0: all KS*KS plane offsets (di, dj); mode 2:
@@ -387,7 +347,7 @@ void ijsum(Tensor Z, c10::optional<Tensor> bias, Tensor y, int64_t ks, int64_t r
   TORCH_CHECK(sgn == 1 || sgn == -1);
   TORCH_CHECK(Z.dim() == 6 && Z.size(0) == ks * ks, "Z must be [ks*ks,V,I,J,K,L]");
   check_shape(y, "y", {Z.size(1), Z.size(2), Z.size(3), Z.size(4), Z.size(5)});
-  if (bias.has_value()) { check(*bias, "bias", at::kFloat); check_shape(*bias, "bias", {1}); }
+  check_opt(bias, "bias", at::kFloat, {1});
   ok(ncnet_ijsum((float*)Z.data_ptr(), opt_ptr<float>(bias), (float*)y.data_ptr(), Z.size(1), Z.size(2), Z.size(3),
                  Z.size(4), Z.size(5), ks, relu ? 1 : 0, (int)sgn, cur_stream(Z)), "ijsum");
 }
@@ -402,7 +362,7 @@ void l2norm_rows(Tensor x, Tensor y, c10::optional<Tensor> inv, double fp8_scale
   check(y, "y", f8 ? at::kFloat8_e4m3fn : h ? at::kHalf : at::kBFloat16);
   TORCH_CHECK(!f8 || fp8_scale > 0, "fp8 output needs fp8_scale > 0");
   TORCH_CHECK(x.dim() == 2 && y.sizes() == x.sizes(), "x,y must be [rows, C]");
-  if (inv.has_value()) { check(*inv, "inv", at::kFloat); check_shape(*inv, "inv", {x.size(0)}); }
+  check_opt(inv, "inv", at::kFloat, {x.size(0)});
   if (y_lo.has_value()) {
     TORCH_CHECK(!f8 && !h, "l2norm_rows: y_lo needs bf16 y");
     check(*y_lo, "y_lo", at::kBFloat16); check_shape(*y_lo, "y_lo", y.sizes().vec());
@@ -481,8 +441,8 @@ void stats_rows(Tensor x, Tensor mx, c10::optional<Tensor> arg, c10::optional<Te
   check(x, "x", at::kFloat); check(mx, "mx", at::kFloat);
   TORCH_CHECK(x.dim() == 3);
   check_shape(mx, "mx", {x.size(0), x.size(1)});
-  if (arg.has_value()) { check(*arg, "arg", at::kInt); check_shape(*arg, "arg", {x.size(0), x.size(1)}); }
-  if (se.has_value()) { check(*se, "se", at::kFloat); check_shape(*se, "se", {x.size(0), x.size(1)}); }
+  check_opt(arg, "arg", at::kInt, {x.size(0), x.size(1)});
+  check_opt(se, "se", at::kFloat, {x.size(0), x.size(1)});
   ok(ncnet_stats_rows((float*)x.data_ptr(), (float*)mx.data_ptr(), arg.has_value() ? (int*)arg->data_ptr() : nullptr,
                       se.has_value() ? (float*)se->data_ptr() : nullptr, x.size(0) * x.size(1), x.size(2),
                       (int)sum_kind, cur_stream(x)),
@@ -495,8 +455,8 @@ void stats_cols(Tensor x, Tensor mx, c10::optional<Tensor> arg, c10::optional<Te
   check(x, "x", at::kFloat); check(mx, "mx", at::kFloat);
   TORCH_CHECK(x.dim() == 3);
   check_shape(mx, "mx", {x.size(0), x.size(2)});
-  if (arg.has_value()) { check(*arg, "arg", at::kInt); check_shape(*arg, "arg", {x.size(0), x.size(2)}); }
-  if (se.has_value()) { check(*se, "se", at::kFloat); check_shape(*se, "se", {x.size(0), x.size(2)}); }
+  check_opt(arg, "arg", at::kInt, {x.size(0), x.size(2)});
+  check_opt(se, "se", at::kFloat, {x.size(0), x.size(2)});
   // few wide columns (InLoc volumes): split the rows over chunks so the grid fills the chip
   const int64_t V = x.size(0), R = x.size(1), C = x.size(2);
   const int64_t blocks = V * ((C + 63) / 64);
@@ -607,7 +567,7 @@ void mm_apply(Tensor c, Tensor rmax, Tensor cmax, c10::optional<Tensor> out, c10
   TORCH_CHECK(c.dim() == 3);
   const int64_t V = c.size(0), R = c.size(1), C = c.size(2);
   check_shape(rmax, "rmax", {V, R}); check_shape(cmax, "cmax", {V, C});
-  if (out.has_value()) { check(*out, "out", at::kFloat); check_shape(*out, "out", {V, R, C}); }
+  check_opt(out, "out", at::kFloat, {V, R, C});
   // out_x / out_xt: bf16 or IEEE half (both the same)
   const bool h = (out_x.has_value() && out_x->scalar_type() == at::kHalf) ||
                  (out_xt.has_value() && out_xt->scalar_type() == at::kHalf);
@@ -619,11 +579,11 @@ void mm_apply(Tensor c, Tensor rmax, Tensor cmax, c10::optional<Tensor> out, c10
     check_ks(pks);
     TORCH_CHECK(!h && I2 * J2 == R && R == C, "mm_apply pad: bf16 planes of a square volume, I2 * J2 = R = C");
     const auto g = pad_geom(I2, J2, pks);
-    if (out_x.has_value()) { check(*out_x, "out_x", xt); check_shape(*out_x, "out_x", {V * R, g[1]}); }
-    if (out_xt.has_value()) { check(*out_xt, "out_xt", xt); check_shape(*out_xt, "out_xt", {V * C, g[1]}); }
+    check_opt(out_x, "out_x", xt, {V * R, g[1]});
+    check_opt(out_xt, "out_xt", xt, {V * C, g[1]});
   } else {
-    if (out_x.has_value()) { check(*out_x, "out_x", xt); check_shape(*out_x, "out_x", {V, R, C}); }
-    if (out_xt.has_value()) { check(*out_xt, "out_xt", xt); check_shape(*out_xt, "out_xt", {V, C, R}); }
+    check_opt(out_x, "out_x", xt, {V, R, C});
+    check_opt(out_xt, "out_xt", xt, {V, C, R});
   }
   ok(ncnet_mm_apply((float*)c.data_ptr(), (float*)rmax.data_ptr(), (float*)cmax.data_ptr(),
                     out.has_value() ? (float*)out->data_ptr() : nullptr, out_x.has_value() ? out_x->data_ptr() : nullptr,
@@ -785,10 +745,8 @@ void conv16f8_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, Tensor Y, int
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   check(X, "X", at::kFloat8_e4m3fn); check(Wp, "Wp", at::kFloat8_e4m3fn);
   check_ks(ks);
-  const bool grp = X.dim() == 7;
-  TORCH_CHECK((X.dim() == 6 || grp) && X.size(-1) == 16, "X must be [V,I,J,K,L,16] or [G,V,I,J,K,L,16]");
-  const int64_t npg = grp ? X.size(0) : 0;
-  std::vector<int64_t> vs(X.sizes().begin() + (grp ? 1 : 0), X.sizes().end());
+  const Vol16 v = vol16(X);
+  const auto& vs = v.vs;
   TORCH_CHECK(epi == 1 || epi == 4, "fp8 conv supports epi 1 (bias+ReLU -> fp8) and 4 (planar fp32)");
   int64_t nco = 16;
   if (epi == 4) {
@@ -799,11 +757,11 @@ void conv16f8_fwd(Tensor X, Tensor Wp, c10::optional<Tensor> bias, Tensor Y, int
   } else {
     check(Y, "Y", at::kFloat8_e4m3fn);
     check_shape(Y, "Y", vs);
-    TORCH_CHECK(bias.has_value()); check(*bias, "bias", at::kFloat); check_shape(*bias, "bias", {16});
+    check_req(bias, "bias", at::kFloat, {16});
   }
-  check_shape(Wp, "Wp", {grp ? npg : ks * ks, conv_pairs16(ks), 64, 8});
+  check_shape(Wp, "Wp", {v.wplanes(ks), conv_pairs16(ks), 64, 8});
   ok(ncnet_conv16f8_fwd(X.data_ptr(), Wp.data_ptr(), opt_ptr<float>(bias), Y.data_ptr(), vs[0], vs[1], vs[2], vs[3],
-                        vs[4], ks, epi, (int)npg, (int)nco, (float)oscale, cur_stream(X)),
+                        vs[4], ks, epi, (int)v.npg, (int)nco, (float)oscale, cur_stream(X)),
      "conv16f8_fwd");
 }
 
@@ -927,7 +885,7 @@ void conv2d_nhwc_x3(Tensor X, Tensor W3, Tensor bias, c10::optional<Tensor> R, T
   check_shape(bias, "bias", {Cout});
   const int64_t Ho = (H + 2 * pad - KH) / stride + 1, Wo = (Wd + 2 * pad - KW) / stride + 1;
   check_shape(Y, "Y", {N, Ho, Wo, 2 * Cout});
-  if (R.has_value()) { check(*R, "R", at::kBFloat16); check_shape(*R, "R", {N, Ho, Wo, 2 * Cout}); }
+  check_opt(R, "R", at::kBFloat16, {N, Ho, Wo, 2 * Cout});
   TORCH_CHECK(N * Ho * Wo < (1LL << 31) && N * H * Wd * 2 * Cin < (1LL << 40), "conv2d_nhwc_x3: sizes exceed int32");
   ok(ncnet_conv2d_nhwc_x3(X.data_ptr(), W3.data_ptr(), (const float*)bias.data_ptr(),
                           R.has_value() ? R->data_ptr() : nullptr, Y.data_ptr(), N, H, Wd, Cin, Cout, KH, KW, stride,

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -142,6 +143,24 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblocks) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// Runtime value -> template argument, the one way launchers select a kernel:
+// dispatch_int<Vs...>(v, f) calls f(std::integral_constant<int, V>{}) for the V
+// of the list equal to v and returns whether one matched.  f is a generic
+// lambda: it is instantiated for every V of the list and for nothing else, so
+// the list IS the set of kernel instantiations (nest calls, with a list per
+// outer value, where a combination must not exist).  A caller that ignores the
+// result says in a comment what confines v to the list: a value outside it
+// launches nothing.
+template <int... Vs, class F>
+static inline bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// both values of a flag: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
 
 // CUs of the current device (persistent grids, tile picking), cached per device
 static inline int device_num_cus() {

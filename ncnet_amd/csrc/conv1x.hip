@@ -35,6 +35,7 @@
 // Reference semantics: lib/conv4d.py:11-51 (same-padded 4D cross-correlation),
 // the first / last NeighConsensus layers of lib/model.py:130-139.
 #include "common.h"
+#include "launchers.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -603,7 +604,6 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
 
 using namespace ncnet;
 
-// padded-plane geometry of a (K, L) plane for kernel size KS: {LP, PPL}
 extern "C" int ncnet_pad_geom(int K, int L, int KS, int* lp, int* ppl) {
   const int P = KS / 2;
   *lp = L + 2 * P;
@@ -611,70 +611,71 @@ extern "C" int ncnet_pad_geom(int K, int L, int KS, int* lp, int* ppl) {
   return 0;
 }
 
-// x: [V, R, C] fp32 or bf16 (x_is_bf16); planes of x (trans 0: N = V*R planes of
-// [I2=K, J2=L]) or of its A<->B swap (trans 1: N = V*C planes of [I2=I, J2=J]) into y
-// [N, PPL] bf16, whose halo the caller zeroed.
 extern "C" int ncnet_pad_planes(const void* x, int x_is_bf16, void* y, int V, int R, int C, int I2, int J2, int KS,
                                 int trans, hipStream_t s) {
   int LP, PPL;
   ncnet_pad_geom(I2, J2, KS, &LP, &PPL);
   const int P = KS / 2;
   bf16* yy = (bf16*)y;
-  if (!trans) {
-    dim3 grid((unsigned)((long long)V * R));
-    if (x_is_bf16) hipLaunchKernelGGL((pad_planes_kernel<bf16, false>), grid, dim3(256), 0, s, (const bf16*)x, yy, V, R, C, I2, J2, LP, PPL, P);
-    else hipLaunchKernelGGL((pad_planes_kernel<float, false>), grid, dim3(256), 0, s, (const float*)x, yy, V, R, C, I2, J2, LP, PPL, P);
-  } else {
-    dim3 grid((unsigned)((long long)V * cdiv(R, 64) * cdiv(C, 64)));
-    if (x_is_bf16) hipLaunchKernelGGL((pad_planes_kernel<bf16, true>), grid, dim3(256), 0, s, (const bf16*)x, yy, V, R, C, I2, J2, LP, PPL, P);
-    else hipLaunchKernelGGL((pad_planes_kernel<float, true>), grid, dim3(256), 0, s, (const float*)x, yy, V, R, C, I2, J2, LP, PPL, P);
-  }
+  // a plane per block, or 64 x 64 transpose tiles
+  const dim3 grid(trans ? (unsigned)((long long)V * cdiv(R, 64) * cdiv(C, 64)) : (unsigned)((long long)V * R));
+  auto launch = [&](auto* xt) {
+    using T = std::remove_pointer_t<decltype(xt)>;
+    dispatch_bool(trans != 0, [&](auto tc) {
+      hipLaunchKernelGGL((pad_planes_kernel<T, decltype(tc)::value>), grid, dim3(256), 0, s, (const T*)x, yy, V, R, C, I2,
+                         J2, LP, PPL, P);
+    });
+  };
+  if (x_is_bf16) launch((bf16*)nullptr); else launch((float*)nullptr);
   return (int)hipGetLastError();
 }
 
 // conv1x16 / wgrad1x16 are instantiated for the training planes: KS 5 at 25 x 25
 // (400 px), 20 x 20 (320 px) and 30 x 30 (480 px: three DMAs per staged copy,
 // 3 output j-planes per item -- 1 in the bf16x3 mode -- to fit LDS), KS 3 at
-// 25 x 25 (the IVD recipe, NC 3,3 / 16,1).  Mirrored in
-// ops/neigh_consensus.py FAST1X_SHAPES.
-template <int KS, int K, int L, int R, bool X3>
+// 25 x 25 (the IVD recipe, NC 3,3 / 16,1).  Mirrored in ops/nc/train.py FAST1X_SHAPES.
+// Calls f(KS, K) as integral constants; false for any other shape.
+template <class F>
+static bool c1x_shape(int KS, int K, int L, F&& f) {
+  bool hit = false;
+  if (K == L)
+    dispatch_int<5, 3>(KS, [&](auto ksc) {
+      if constexpr (decltype(ksc)::value == 5) hit = dispatch_int<25, 20, 30>(K, [&](auto kc) { f(ksc, kc); });
+      else hit = dispatch_int<25>(K, [&](auto kc) { f(ksc, kc); });
+    });
+  return hit;
+}
+
+// conv1x16_kernel<KS, R, EPI, K, L, PD>: R output j-planes per item (5; 3 at 30 x 30 and in
+// the bf16x3 mode, where both weight sets sit in LDS; 1 for both), PD the
+// transposed-read lookahead (tuning c1x_pd 2 / 3: the bf16 KS 5 25 x 25 kernel only, else 1).
+template <int KS, int K, bool X3>
 static void c1x_launch(int epi, int V, int I, int J, const bf16* x, const u32x4* w, const float* bias, const bf16* m,
                        bf16* y, int nt_store, long long xlo, long long ylo, hipStream_t s) {
+  constexpr int L = K, R = X3 ? (K == 30 ? 1 : 3) : (K == 30 ? 3 : 5);
   using C = C1X<KS, K, L>;
   const int nitems = V * I * cdiv(J, R);
   dim3 grid((unsigned)std::min(nitems, device_num_cus())), block(512);   // persistent: one workgroup per CU
   // X3: both weight sets ahead of the planes
   constexpr size_t lds = (size_t)C::lds(R + KS - 1, 1) + (X3 ? (size_t)C::NT * 1024 : 0);
   static_assert(lds <= 160 * 1024, "LDS");
-  auto go = [&](auto ec) {
-    constexpr int E = decltype(ec)::value;
-    if constexpr (!X3 && KS == 5 && K == 25) {
-      if (tuning().c1x_pd == 2) {
-        hipLaunchKernelGGL((conv1x16_kernel<KS, R, E, K, L, 2>), grid, block, lds, s, x, w, bias, m, y, V, I, J,
-                           nt_store, xlo, ylo);
-        return;
-      }
-      if (tuning().c1x_pd == 3) {
-        hipLaunchKernelGGL((conv1x16_kernel<KS, R, E, K, L, 3>), grid, block, lds, s, x, w, bias, m, y, V, I, J,
-                           nt_store, xlo, ylo);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((conv1x16_kernel<KS, R, E, K, L>), grid, block, lds, s, x, w, bias, m, y, V, I, J, nt_store, xlo,
-                       ylo);
+  auto go = [&](auto ec, auto pdc) {
+    hipLaunchKernelGGL((conv1x16_kernel<KS, R, decltype(ec)::value, K, L, decltype(pdc)::value>), grid, block, lds, s, x,
+                       w, bias, m, y, V, I, J, nt_store, xlo, ylo);
   };
-  if constexpr (X3) {
-    if ((epi & ~EPI1X_X3) == EPI1X_BIAS_RELU) go(std::integral_constant<int, EPI1X_BIAS_RELU | EPI1X_X3>{});
-    else go(std::integral_constant<int, EPI1X_MASK | EPI1X_X3>{});
-  } else {
-    if (epi == EPI1X_BIAS_RELU) go(std::integral_constant<int, EPI1X_BIAS_RELU>{});
-    else go(std::integral_constant<int, EPI1X_MASK>{});
-  }
+  constexpr int X3F = X3 ? EPI1X_X3 : 0;
+  const int e = (epi & ~EPI1X_X3) == EPI1X_BIAS_RELU ? EPI1X_BIAS_RELU : EPI1X_MASK;   // (checked by the caller)
+  dispatch_int<EPI1X_BIAS_RELU | X3F, EPI1X_MASK | X3F>(e | X3F, [&](auto ec) {
+    if constexpr (!X3 && KS == 5 && K == 25) {
+      const int pd = tuning().c1x_pd;
+      dispatch_int<2, 3, 1>(pd == 2 || pd == 3 ? pd : 1, [&](auto pdc) { go(ec, pdc); });
+    } else {
+      go(ec, std::integral_constant<int, 1>{});
+    }
+  });
 }
 
-// returns -1 when the shape has no instantiation.  epi | 4 (EPI1X_X3): the
-// bf16x3 layer (X_lo = Xp + xlo, Wa = [hi; lo] fragment sets, Y_lo = Y + ylo,
-// elements); it runs 3 output j-planes per item (both weight sets in LDS).
+// The bf16x3 layer runs 3 output j-planes per item (both weight sets in LDS).
 extern "C" int ncnet_conv1x16(const void* Xp, const void* Wa, const float* bias, const void* M, void* Y, int V, int I,
                               int J, int K, int L, int KS, int epi, int nt_store, long long xlo, long long ylo,
                               hipStream_t s) {
@@ -682,45 +683,28 @@ extern "C" int ncnet_conv1x16(const void* Xp, const void* Wa, const float* bias,
   const bool x3 = (epi & EPI1X_X3) != 0;
   if (e != EPI1X_BIAS_RELU && e != EPI1X_MASK) return -3;
   const bf16* x = (const bf16*)Xp; const u32x4* w = (const u32x4*)Wa; const bf16* m = (const bf16*)M; bf16* y = (bf16*)Y;
-  if (KS == 5 && K == 25 && L == 25) {
-    if (x3) c1x_launch<5, 25, 25, 3, true>(epi, V, I, J, x, w, bias, m, y, 0, xlo, ylo, s);
-    else c1x_launch<5, 25, 25, 5, false>(epi, V, I, J, x, w, bias, m, y, nt_store, 0, 0, s);
-  } else if (KS == 5 && K == 20 && L == 20) {
-    if (x3) c1x_launch<5, 20, 20, 3, true>(epi, V, I, J, x, w, bias, m, y, 0, xlo, ylo, s);
-    else c1x_launch<5, 20, 20, 5, false>(epi, V, I, J, x, w, bias, m, y, nt_store, 0, 0, s);
-  } else if (KS == 5 && K == 30 && L == 30) {
-    if (x3) c1x_launch<5, 30, 30, 1, true>(epi, V, I, J, x, w, bias, m, y, 0, xlo, ylo, s);
-    else c1x_launch<5, 30, 30, 3, false>(epi, V, I, J, x, w, bias, m, y, nt_store, 0, 0, s);
-  } else if (KS == 3 && K == 25 && L == 25) {
-    if (x3) c1x_launch<3, 25, 25, 3, true>(epi, V, I, J, x, w, bias, m, y, 0, xlo, ylo, s);
-    else c1x_launch<3, 25, 25, 5, false>(epi, V, I, J, x, w, bias, m, y, nt_store, 0, 0, s);
-  } else return -1;
+  if (!c1x_shape(KS, K, L, [&](auto ksc, auto kc) {
+        constexpr int KSV = decltype(ksc)::value, KV = decltype(kc)::value;
+        if (x3) c1x_launch<KSV, KV, true>(epi, V, I, J, x, w, bias, m, y, 0, xlo, ylo, s);
+        else c1x_launch<KSV, KV, false>(epi, V, I, J, x, w, bias, m, y, nt_store, 0, 0, s);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
-template <int KS, int K, int L>
-static void w1x_launch(int G, int V, int I, int J, const bf16* d, const bf16* x, float* part, float* partb,
-                       hipStream_t s) {
-  using C = W1X<KS, K, L>;
-  if (partb)
-    hipLaunchKernelGGL((wgrad1x16_kernel<KS, K, L, true>), dim3((unsigned)G), dim3(512), (size_t)C::LDS, s, d, x, part,
-                       partb, V, I, J);
-  else
-    hipLaunchKernelGGL((wgrad1x16_kernel<KS, K, L, false>), dim3((unsigned)G), dim3(512), (size_t)C::LDS, s, d, x,
-                       part, partb, V, I, J);
-}
-
-// wgrad1x16: D bf16 [V,I,J,K,L,16], X1 padded planes [V*I*J][PPL]; part fp32
-// [G][KS*KS taps][32 combos][16] (one partial per workgroup, G <= the CU count),
-// partb fp32 [G][16] (sum of D; null: none).  Returns -1 for shapes without an instantiation.
+// wgrad1x16_kernel<KS, K, L, BIAS = partb given>
 extern "C" int ncnet_wgrad1x16(const void* Dp, const void* X1p, float* part, float* partb, int G, int V, int I, int J,
                                int K, int L, int KS, hipStream_t s) {
   if (G < 1) return -2;
   const bf16* d = (const bf16*)Dp; const bf16* x = (const bf16*)X1p;
-  if (KS == 5 && K == 25 && L == 25) w1x_launch<5, 25, 25>(G, V, I, J, d, x, part, partb, s);
-  else if (KS == 5 && K == 20 && L == 20) w1x_launch<5, 20, 20>(G, V, I, J, d, x, part, partb, s);
-  else if (KS == 5 && K == 30 && L == 30) w1x_launch<5, 30, 30>(G, V, I, J, d, x, part, partb, s);
-  else if (KS == 3 && K == 25 && L == 25) w1x_launch<3, 25, 25>(G, V, I, J, d, x, part, partb, s);
-  else return -1;
+  if (!c1x_shape(KS, K, L, [&](auto ksc, auto kc) {
+        constexpr int KSV = decltype(ksc)::value, KV = decltype(kc)::value;
+        const size_t lds = (size_t)W1X<KSV, KV, KV>::LDS;
+        dispatch_bool(partb != nullptr, [&](auto bc) {
+          hipLaunchKernelGGL((wgrad1x16_kernel<KSV, KV, KV, decltype(bc)::value>), dim3((unsigned)G), dim3(512), lds, s,
+                             d, x, part, partb, V, I, J);
+        });
+      }))
+    return -1;
   return (int)hipGetLastError();
 }

@@ -17,6 +17,7 @@
 // (MIOpen: conv + separate bias pass + PyTorch ReLU / add passes).
 // Requires Cin % 64 == 0 and Cout % 64 == 0 (every ResNet conv but the stem).
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
 namespace ncnet {
@@ -629,22 +630,8 @@ __global__ __launch_bounds__(512, 1) void conv2d_nhwc_v3_kernel(Conv2dArgs p) {
 }
 
 static int c3_pick_tm(int M, int Cout, int Cin, int TN, int ncu, long long* cost);
-// mode 0: bf16, 1: IEEE half, 2: bf16x3
-template <int TM, int TN>
-static void c3_launch1(int mode, dim3 g, dim3 b, hipStream_t stream, const Conv2dArgs& p) {
-  const size_t lds = (size_t)cv3::Geo<TM, TN>::LDS;
-  if (mode == 1) hipLaunchKernelGGL((conv2d_nhwc_v3_kernel<TM, TN, true, false>), g, b, lds, stream, p);
-  else if (mode == 2) hipLaunchKernelGGL((conv2d_nhwc_v3_kernel<TM, TN, false, true>), g, b, lds, stream, p);
-  else hipLaunchKernelGGL((conv2d_nhwc_v3_kernel<TM, TN, false, false>), g, b, lds, stream, p);
-}
-template <int TN>
-static void c3_launch(int tm, int mode, dim3 g, dim3 b, hipStream_t stream, const Conv2dArgs& p) {
-  if (tm == 3) c3_launch1<3, TN>(mode, g, b, stream, p);
-  else if (tm == 4) c3_launch1<4, TN>(mode, g, b, stream, p);
-  else if (tm == 5) c3_launch1<5, TN>(mode, g, b, stream, p);
-  else c3_launch1<6, TN>(mode, g, b, stream, p);
-}
-// launch v3 with its tile choice; false when it does not apply
+// launch v3 with its tile choice, conv2d_nhwc_v3_kernel<TM 3..6, TN 4 / 2 / 1, F16, X3>;
+// false when it does not apply.  mode 0: bf16, 1: IEEE half, 2: bf16x3
 static bool c3_run(Conv2dArgs& p, int mode, hipStream_t stream) {
   const int TNv = (p.Cout % 256 == 0) ? 4 : (p.Cout % 128 == 0) ? 2 : 1;
   const int tm = c3_pick_tm(p.M, p.Cout, p.Ck, TNv, device_num_cus(), nullptr);
@@ -652,9 +639,16 @@ static bool c3_run(Conv2dArgs& p, int mode, hipStream_t stream) {
   p.tiles_n = p.Cout / (64 * TNv);
   p.tiles_m = cdiv(p.M, 16 * tm);
   dim3 g3((unsigned)(p.tiles_m * p.tiles_n)), b3(512);
-  if (TNv == 4) c3_launch<4>(tm, mode, g3, b3, stream, p);
-  else if (TNv == 2) c3_launch<2>(tm, mode, g3, b3, stream, p);
-  else c3_launch<1>(tm, mode, g3, b3, stream, p);
+  dispatch_int<4, 2, 1>(TNv, [&](auto tnc) {   // TNv is 4, 2 or 1 (above)
+    dispatch_int<3, 4, 5, 6>(tm, [&](auto tmc) {   // c3_pick_tm's range
+      constexpr int TM = decltype(tmc)::value, TN = decltype(tnc)::value;
+      const size_t lds = (size_t)cv3::Geo<TM, TN>::LDS;
+      dispatch_int<1, 2, 0>(mode == 1 || mode == 2 ? mode : 0, [&](auto mc) {
+        constexpr int MODE = decltype(mc)::value;
+        hipLaunchKernelGGL((conv2d_nhwc_v3_kernel<TM, TN, MODE == 1, MODE == 2>), g3, b3, lds, stream, p);
+      });
+    });
+  });
   return true;
 }
 
@@ -679,7 +673,6 @@ static int c3_pick_tm(int M, int Cout, int Cin, int TN, int ncu, long long* cost
 
 using namespace ncnet;
 
-// f16: X / W / R / Y are IEEE half (else bf16).
 extern "C" int ncnet_conv2d_nhwc(const void* X, const void* W, const float* bias, const void* R, void* Y, int N, int H,
                                  int Wd, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int f16,
                                  hipStream_t stream) {
@@ -734,29 +727,34 @@ extern "C" int ncnet_conv2d_nhwc(const void* X, const void* W, const float* bias
     p.tiles_m = cdiv(p.M, 256);
     dim3 g2((unsigned)(p.tiles_m * p.tiles_n)), b2(512);
     const size_t lds = (size_t)3 * (256 + BN) * 64;
-    if (f16) hipLaunchKernelGGL((conv2d_nhwc_v2_kernel<256, 128, 8, 3, true>), g2, b2, lds, stream, p);
-    else hipLaunchKernelGGL((conv2d_nhwc_v2_kernel<256, 128, 8, 3>), g2, b2, lds, stream, p);
+    dispatch_bool(f16 != 0, [&](auto hc) {
+      hipLaunchKernelGGL((conv2d_nhwc_v2_kernel<256, 128, 8, 3, decltype(hc)::value>), g2, b2, lds, stream, p);
+    });
     return (int)hipGetLastError();
   }
-  if (variant == 2 && !f16) {
+  // the (BM, BN) tile of the two small-tile kernels, 128 / 64 each
+  auto with_tile = [&](auto&& f) {
+    dispatch_int<128, 64>(BM, [&](auto bmc) { dispatch_int<128, 64>(BN, [&](auto bnc) { f(bmc, bnc); }); });   // BM, BN are 128 or 64 (above)
+  };
+  if (variant == 2 && !f16) {   // forced DMA ring at the small tiles
     const size_t lds = (size_t)4 * (BM + BN) * 64;
-#define LC3(BMV, BNV) hipLaunchKernelGGL((conv2d_nhwc_v2_kernel<BMV, BNV, 4, 4>), grid, block, lds, stream, p)
-    if (BM == 128) { if (BN == 128) LC3(128, 128); else LC3(128, 64); }
-    else { if (BN == 128) LC3(64, 128); else LC3(64, 64); }
-#undef LC3
+    with_tile([&](auto bmc, auto bnc) {
+      hipLaunchKernelGGL((conv2d_nhwc_v2_kernel<decltype(bmc)::value, decltype(bnc)::value, 4, 4>), grid, block, lds, stream,
+                         p);
+    });
     return (int)hipGetLastError();
   }
-  const size_t lds = (size_t)(BM + BN) * 128;
-#define LC2(BMV, BNV) do { if (f16) hipLaunchKernelGGL((conv2d_nhwc_kernel<BMV, BNV, true>), grid, block, lds, stream, p); \
-                           else hipLaunchKernelGGL((conv2d_nhwc_kernel<BMV, BNV>), grid, block, lds, stream, p); } while (0)
-  if (BM == 128) { if (BN == 128) LC2(128, 128); else LC2(128, 64); }
-  else { if (BN == 128) LC2(64, 128); else LC2(64, 64); }
-#undef LC2
+  const size_t lds = (size_t)(BM + BN) * 128;   // v1, register-staged
+  with_tile([&](auto bmc, auto bnc) {
+    dispatch_bool(f16 != 0, [&](auto hc) {
+      hipLaunchKernelGGL((conv2d_nhwc_kernel<decltype(bmc)::value, decltype(bnc)::value, decltype(hc)::value>), grid, block,
+                         lds, stream, p);
+    });
+  });
   return (int)hipGetLastError();
 }
 
-// bf16x3 (fp32-accurate) conv: X [N,H,W,2 Cin] = [hi | lo] bf16 pairs, W [Cout][KH][KW][3 Cin]
-// = [W_hi | W_hi | W_lo], R / Y [.., 2 Cout] pairs, bias fp32 (conv2d_nhwc_v3 X3).
+// conv2d_nhwc_v3 X3 only
 extern "C" int ncnet_conv2d_nhwc_x3(const void* X, const void* W, const float* bias, const void* R, void* Y, int N,
                                     int H, int Wd, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu,
                                     hipStream_t stream) {

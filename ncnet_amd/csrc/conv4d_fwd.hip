@@ -15,8 +15,9 @@
 //   Cin=16 -> Cout=16 : MFMA D[co][voxel], K = 2 taps x 16 ci (conv16v2 / v3).
 //   The 1-channel layers run on the same kernels through the ij encoding
 //   (csrc/jshift.hip): group-plane mode, in-plane (dk, dl) taps only.
-//   Wider layers are channel blocks of 16 (ops/neigh_consensus.py).
+//   Wider layers are channel blocks of 16 (ops/nc/layers.py).
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_fp8.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -1114,37 +1115,27 @@ using namespace ncnet;
 
 // conv16v4 at the compile-time tiles it is instantiated for: the
 // --image_size 240 / 320 / 400 training planes (15, 20, 25: one whole-plane
-// tile) and 480 (30 x 30: two 30 x 15 tiles) at KS 5 and KS 3.
-template <int KS, int TK, int TL>
-static void v4_launch1(int epi, dim3 grid, dim3 block, hipStream_t stream, const bf16* x, const u32x4* w,
-                       const float* bias, const bf16* m, bf16* y, const ConvGeom& g) {
-  constexpr int R = 5, NQ = (KS * KS + 1) / 2;
-  const size_t lds = 3 * (size_t)(TK + KS - 1) * (TL + ((KS - 1 + 7) / 8) * 8) * 32 + (size_t)KS * NQ * 1024 + 1024;
-  auto go = [&](auto ec) {
-    constexpr int E = decltype(ec)::value;
-    hipLaunchKernelGGL((conv16v4_fwd_kernel<KS, R, E, TK, TL>), grid, block, lds, stream, x, w, bias, m, y, g);
-  };
-  if (epi == EPI_BIAS_RELU) go(std::integral_constant<int, EPI_BIAS_RELU>{});
-  else if (epi == EPI_MASK) go(std::integral_constant<int, EPI_MASK>{});
-  else if (epi == (EPI_BIAS_RELU | EPI_X3)) go(std::integral_constant<int, EPI_BIAS_RELU | EPI_X3>{});
-  else go(std::integral_constant<int, EPI_MASK | EPI_X3>{});
-}
-template <int KS>
-static bool v4_launch_ks(int K, int L, int tk, int tl, int epi, dim3 grid, dim3 block, hipStream_t stream,
-                         const bf16* x, const u32x4* w, const float* bias, const bf16* m, bf16* y, const ConvGeom& g) {
-  if (K != L) return false;
-  if (K == 25 && tk == 25 && tl == 25) v4_launch1<KS, 25, 25>(epi, grid, block, stream, x, w, bias, m, y, g);
-  else if (K == 20 && tk == 20 && tl == 20) v4_launch1<KS, 20, 20>(epi, grid, block, stream, x, w, bias, m, y, g);
-  else if (K == 15 && tk == 15 && tl == 15) v4_launch1<KS, 15, 15>(epi, grid, block, stream, x, w, bias, m, y, g);
-  else if (K == 30 && tk == 30 && tl == 15) v4_launch1<KS, 30, 15>(epi, grid, block, stream, x, w, bias, m, y, g);
-  else return false;
-  return true;
-}
+// tile) and 480 (30 x 30: two 30 x 15 tiles) at KS 5 and KS 3, with the four
+// bias / mask (x bf16x3) epilogues.  False (nothing launched) for any other shape.
 static bool v4_launch(int KS, int K, int L, int tk, int tl, int epi, dim3 grid, dim3 block, hipStream_t stream,
                       const bf16* x, const u32x4* w, const float* bias, const bf16* m, bf16* y, const ConvGeom& g) {
-  if (KS == 5) return v4_launch_ks<5>(K, L, tk, tl, epi, grid, block, stream, x, w, bias, m, y, g);
-  if (KS == 3) return v4_launch_ks<3>(K, L, tk, tl, epi, grid, block, stream, x, w, bias, m, y, g);
-  return false;
+  if (K != L) return false;
+  // (an epi outside the four runs the x3 mask epilogue, as it always has; no binding passes one)
+  const int e4 = epi == EPI_BIAS_RELU || epi == EPI_MASK || epi == (EPI_BIAS_RELU | EPI_X3) ? epi : EPI_MASK | EPI_X3;
+  bool hit = false;
+  dispatch_int<5, 3>(KS, [&](auto ksc) {
+    dispatch_int<25, 20, 15, 30>(K, [&](auto kc) {
+      constexpr int KSV = decltype(ksc)::value, TK = decltype(kc)::value, TL = TK == 30 ? 15 : TK;
+      constexpr int R = 5, NQ = (KSV * KSV + 1) / 2;
+      if (tk != TK || tl != TL) return;
+      const size_t lds = 3 * (size_t)(TK + KSV - 1) * (TL + ((KSV - 1 + 7) / 8) * 8) * 32 + (size_t)KSV * NQ * 1024 + 1024;
+      hit = dispatch_int<EPI_BIAS_RELU, EPI_MASK, EPI_BIAS_RELU | EPI_X3, EPI_MASK | EPI_X3>(e4, [&](auto ec) {
+        hipLaunchKernelGGL((conv16v4_fwd_kernel<KSV, R, decltype(ec)::value, TK, TL>), grid, block, lds, stream, x, w,
+                           bias, m, y, g);
+      });
+    });
+  });
+  return hit;
 }
 
 // Tile choice: the whole (k,l) plane when it fits (<= 25 x 25 output); planes
@@ -1164,20 +1155,14 @@ static void pick_tile(int K, int L, int& tk, int& tl) {
 // output j-tiles per workgroup of the group-plane conv
 static int gp_tpw() { return tuning().gp_tpw; }
 
+// Kernel selection of ncnet_conv16_fwd, top to bottom:
+//  1. npg == 0, bias / mask epilogue, KS 5 / 3 -- the full (di, dj) sum with R = 5
+//     output j-planes per workgroup: conv16v4 at its compile-time planes
+//     (v4_launch), else conv16v3; a bf16x3 layer v4 does not cover goes to 2.
+//  2. bf16x3 on conv16v2 (its three phases): group planes, or the fallback of 1.
+//  3. conv16v2: every other case (any KS and epilogue, group planes).
 // KS = 5 and 3 are NC-Net's kernel sizes (lib/model.py:125-139 defaults, the
 // InLoc and PF-Pascal checkpoints); 1 and 7 complete the general Conv4d.
-#define KS_DISPATCH(M, ...) \
-  do { if (KS == 5) M(5, __VA_ARGS__); else if (KS == 3) M(3, __VA_ARGS__); \
-       else if (KS == 7) M(7, __VA_ARGS__); else if (KS == 1) M(1, __VA_ARGS__); else return -2; } while (0)
-
-// X [V,I,J,K,L,16] (all KS*KS planes (i+di-P, j+dj-P)), or npg > 0: group-planes
-// mode -- X holds npg input groups [npg][V,I,J,K,L,16] and
-// Y = sum_s conv_(dk,dl)(X[s] plane (i,j), Wp plane s): the (di, dj) offsets
-// live in the channels (ij encoding, csrc/jshift.hip) or s indexes 16-channel
-// input blocks of a wider layer.
-//
-// epi | EPI_X3 (KS 3 / 5, epi 1 or 2): the bf16x3 layer, X_lo = X + xlo,
-// Wp = [hi planes; lo planes], split output Y / Y + ylo (elements).
 extern "C" int ncnet_conv16_fwd(const void* X, const void* Wp, const float* bias, const void* M, void* Y,
                                 int V, int I, int J, int K, int L, int KS, int epi, int npg, int nco,
                                 long long xlo, long long ylo, hipStream_t stream) {
@@ -1197,56 +1182,62 @@ extern "C" int ncnet_conv16_fwd(const void* X, const void* Wp, const float* bias
   g.RS = tl + ((KS - 1 + 7) / 8) * 8;
   const int nq = (KS * KS + 1) / 2;
   const bf16* x = (const bf16*)X; const u32x4* w = (const u32x4*)Wp; const bf16* m = (const bf16*)M; bf16* y = (bf16*)Y;
+
+  // 1. full (di, dj) sum: R = 5 output j-planes per workgroup, X reused across dj
   if (npg == 0 && (epi & ~EPI_X3) != EPI_NONE && (epi & ~EPI_X3) != EPI_F32X16 && (KS == 5 || KS == 3)) {
-    // full (di, dj) sum: R = 5 output j-planes per workgroup, X reused across dj
     constexpr int R = 5;
-    const int njb1 = g.njb;
-    g.njb = cdiv(J, R);
-    dim3 grid3((unsigned)(V * I * g.njb * g.nkt * g.nlt)), block3(512);
-    if (!tuning().conv_v3 && v4_launch(KS, K, L, tk, tl, epi, grid3, block3, stream, x, w, bias, m, y, g))
+    ConvGeom g3 = g;
+    g3.njb = cdiv(J, R);
+    dim3 grid3((unsigned)(V * I * g3.njb * g3.nkt * g3.nlt)), block3(512);
+    if (!tuning().conv_v3 && v4_launch(KS, K, L, tk, tl, epi, grid3, block3, stream, x, w, bias, m, y, g3))
       return (int)hipGetLastError();
-    g.njb = njb1;
-    if (x3) goto v2_x3;   // other shapes: the v2 kernel's phases
-    g.njb = cdiv(J, R);
-    size_t lds3 = 2 * (size_t)g.PR * g.RS * 32 + (size_t)KS * nq * 1024;
-#define L16V3(KSV, EPIV) hipLaunchKernelGGL((conv16v3_fwd_kernel<KSV, R, EPIV>), grid3, block3, lds3, stream, x, w, bias, m, y, g)
-    if (KS == 5) { if (epi == EPI_BIAS_RELU) L16V3(5, EPI_BIAS_RELU); else L16V3(5, EPI_MASK); }
-    else { if (epi == EPI_BIAS_RELU) L16V3(3, EPI_BIAS_RELU); else L16V3(3, EPI_MASK); }
-#undef L16V3
-    return (int)hipGetLastError();
+    if (!x3) {
+      size_t lds3 = 2 * (size_t)g3.PR * g3.RS * 32 + (size_t)KS * nq * 1024;
+      const int e3 = epi == EPI_BIAS_RELU ? EPI_BIAS_RELU : EPI_MASK;
+      dispatch_int<5, 3>(KS, [&](auto ksc) {
+        dispatch_int<EPI_BIAS_RELU, EPI_MASK>(e3, [&](auto ec) {
+          hipLaunchKernelGGL((conv16v3_fwd_kernel<decltype(ksc)::value, R, decltype(ec)::value>), grid3, block3, lds3,
+                             stream, x, w, bias, m, y, g3);
+        });
+      });
+      return (int)hipGetLastError();
+    }
+    // x3 at other shapes: the v2 kernel's phases
   }
-v2_x3: {
+
+  // 2 / 3. conv16v2.  Group planes: tpw consecutive output j-tiles per workgroup
+  // (NCNET_GP_TPW, default 5): the next tile's first plane DMA overlaps the current epilogue
   size_t lds2 = 2 * (size_t)g.PR * g.RS * 32 + (size_t)nq * 1024;
-  // group planes: tpw consecutive output j-tiles per workgroup (NCNET_GP_TPW,
-  // default 5): the next tile's first plane DMA overlaps the current epilogue
   const bool mt = npg > 0 && gp_tpw() > 1;
   if (mt) { g.tpw = gp_tpw(); g.njb = cdiv(J, g.tpw); }
   dim3 grid2((unsigned)(V * I * g.njb * g.nkt * g.nlt)), block2(512);
-  if (x3) {
-#define L16V2X(KSV, EPIV) do { if (mt) hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPIV, true>), grid2, block2, lds2, stream, x, w, bias, m, y, g); \
-                               else hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPIV, false>), grid2, block2, lds2, stream, x, w, bias, m, y, g); } while (0)
-    if (KS == 5) { if (epi == (EPI_BIAS_RELU | EPI_X3)) L16V2X(5, EPI_BIAS_RELU | EPI_X3); else L16V2X(5, EPI_MASK | EPI_X3); }
-    else { if (epi == (EPI_BIAS_RELU | EPI_X3)) L16V2X(3, EPI_BIAS_RELU | EPI_X3); else L16V2X(3, EPI_MASK | EPI_X3); }
-#undef L16V2X
+  auto launch_v2 = [&](auto ksc, auto ec) {
+    dispatch_bool(mt, [&](auto mtc) {
+      hipLaunchKernelGGL((conv16v2_fwd_kernel<decltype(ksc)::value, decltype(ec)::value, decltype(mtc)::value>), grid2,
+                         block2, lds2, stream, x, w, bias, m, y, g);
+    });
+  };
+  if (x3) {   // 2. KS 5 / 3, bias or mask (checked above)
+    const int ex = epi == (EPI_BIAS_RELU | EPI_X3) ? epi : EPI_MASK | EPI_X3;
+    dispatch_int<5, 3>(KS, [&](auto ksc) {   // x3: KS is 5 or 3 (checked at the top)
+      dispatch_int<EPI_BIAS_RELU | EPI_X3, EPI_MASK | EPI_X3>(ex, [&](auto ec) { launch_v2(ksc, ec); });
+    });
     return (int)hipGetLastError();
   }
-#define L16V2E(KSV, EPIV) do { if (mt) hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPIV, true>), grid2, block2, lds2, stream, x, w, bias, m, y, g); \
-                               else hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPIV, false>), grid2, block2, lds2, stream, x, w, bias, m, y, g); } while (0)
-#define L16V2(KSV, _) do { if (epi == EPI_BIAS_RELU) L16V2E(KSV, EPI_BIAS_RELU); else if (epi == EPI_MASK) L16V2E(KSV, EPI_MASK); \
-                           else if (epi == EPI_F32X16) L16V2E(KSV, EPI_F32X16); else L16V2E(KSV, EPI_NONE); } while (0)
-  KS_DISPATCH(L16V2, 0);
-#undef L16V2
-#undef L16V2E
+  // 3. (an epi outside the four runs the plain epilogue)
+  const int e2 = epi == EPI_BIAS_RELU || epi == EPI_MASK || epi == EPI_F32X16 ? epi : EPI_NONE;
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        dispatch_int<EPI_BIAS_RELU, EPI_MASK, EPI_F32X16, EPI_NONE>(e2, [&](auto ec) { launch_v2(ksc, ec); });
+      }))
+    return -2;
   return (int)hipGetLastError();
 }
-}
 
-// Cout = 1 layer (16 input channels) in output-plane-block mode: Y fp32
-// [V,I,J,K,L] = act(bias + conv(X, W)); Wp [(KS+3)^2 relative planes][nq][64][8]
-// (ops/packing.py blk_out_weights): the 16 MFMA rows are a 4 x 4 block of output
-// planes, so every input plane staged in LDS feeds up to 16 output planes and
-// no combo-planar partials (ij encoding + ijsum) round-trip HBM.
-// xlo >= 0 ... any value with x3 != 0: the bf16x3 layer (X_lo = X + xlo, Wp = [hi; lo] planes).
+// Cout = 1 layer in output-plane-block mode: the 16 MFMA rows are a 4 x 4 block
+// of output planes, so every input plane staged in LDS feeds up to 16 output
+// planes and no combo-planar partials (ij encoding + ijsum) round-trip HBM.
+// Kernel: conv16v2 with the EPI_BLK1 epilogue (| EPI_X3 at KS 5 / 3), with the
+// compile-time plane CT = 25 for the KS 5 400 px training planes.
 extern "C" int ncnet_conv16_blk_fwd(const void* X, const void* Wp, const float* bias, float* Y, int V, int I, int J,
                                     int K, int L, int KS, int relu, int x3, long long xlo, hipStream_t stream) {
   int tk, tl;
@@ -1262,28 +1253,27 @@ extern "C" int ncnet_conv16_blk_fwd(const void* X, const void* Wp, const float* 
   size_t lds2 = 2 * (size_t)g.PR * g.RS * 32 + (size_t)nq * 1024;
   dim3 grid((unsigned)(V * g.nib * g.njb * g.nkt * g.nlt)), block(512);
   const bf16* x = (const bf16*)X; const u32x4* w = (const u32x4*)Wp;
+  auto launch = [&](auto ksc, auto ec, auto ctc) {
+    hipLaunchKernelGGL((conv16v2_fwd_kernel<decltype(ksc)::value, decltype(ec)::value, false, decltype(ctc)::value>),
+                       grid, block, lds2, stream, x, w, bias, nullptr, (bf16*)Y, g);
+  };
+  using Blk = std::integral_constant<int, EPI_BLK1>;
+  using BlkX3 = std::integral_constant<int, EPI_BLK1 | EPI_X3>;
+  using CT0 = std::integral_constant<int, 0>;
   if (KS == 5 && K == 25 && L == 25 && tk == 25 && tl == 25) {   // the 400 px training planes
-    if (x3)
-      hipLaunchKernelGGL((conv16v2_fwd_kernel<5, EPI_BLK1 | EPI_X3, false, 25>), grid, block, lds2, stream, x, w, bias,
-                         nullptr, (bf16*)Y, g);
-    else
-      hipLaunchKernelGGL((conv16v2_fwd_kernel<5, EPI_BLK1, false, 25>), grid, block, lds2, stream, x, w, bias, nullptr,
-                         (bf16*)Y, g);
+    using KS5 = std::integral_constant<int, 5>;
+    using CT25 = std::integral_constant<int, 25>;
+    if (x3) launch(KS5{}, BlkX3{}, CT25{}); else launch(KS5{}, Blk{}, CT25{});
     return (int)hipGetLastError();
   }
-#define LBLK(KSV, _) hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPI_BLK1, false>), grid, block, lds2, stream, x, w, bias, nullptr, (bf16*)Y, g)
-#define LBLKX(KSV) hipLaunchKernelGGL((conv16v2_fwd_kernel<KSV, EPI_BLK1 | EPI_X3, false>), grid, block, lds2, stream, x, w, bias, nullptr, (bf16*)Y, g)
   if (x3) {
-    if (KS == 5) LBLKX(5); else LBLKX(3);
+    dispatch_int<5, 3>(KS, [&](auto ksc) { launch(ksc, BlkX3{}, CT0{}); });   // x3: KS is 5 or 3 (checked above)
     return (int)hipGetLastError();
   }
-#undef LBLKX
-  KS_DISPATCH(LBLK, 0);
-#undef LBLK
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) { launch(ksc, Blk{}, CT0{}); })) return -2;
   return (int)hipGetLastError();
 }
 
-// fp8 (OCP e4m3) inference Conv4d 16 -> 16; epi 1 (fp8 out) or 4 (planar fp32), oscale = 1 / weight scale.
 extern "C" int ncnet_conv16f8_fwd(const void* X, const void* Wp, const float* bias, void* Y, int V, int I, int J, int K,
                                   int L, int KS, int epi, int npg, int nco, float oscale, hipStream_t stream) {
   int tk, tl;
@@ -1299,11 +1289,14 @@ extern "C" int ncnet_conv16f8_fwd(const void* X, const void* Wp, const float* bi
   size_t lds = 2 * (size_t)g.PR * g.RS * 16 + (size_t)nq * 512;
   dim3 grid((unsigned)(V * I * J * g.nkt * g.nlt)), block(512);
   const uint8_t* x = (const uint8_t*)X; const uint8_t* w = (const uint8_t*)Wp;
-#define LF8(KSV, _) do { if (epi == EPI_BIAS_RELU) hipLaunchKernelGGL((conv16f8_fwd_kernel<KSV, EPI_BIAS_RELU>), grid, block, lds, stream, x, w, bias, Y, g); \
-                         else if (epi == EPI_F32X16) hipLaunchKernelGGL((conv16f8_fwd_kernel<KSV, EPI_F32X16>), grid, block, lds, stream, x, w, bias, Y, g); \
-                         else return -2; } while (0)
-  KS_DISPATCH(LF8, 0);
-#undef LF8
+  bool epi_ok = false;
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        epi_ok = dispatch_int<EPI_BIAS_RELU, EPI_F32X16>(epi, [&](auto ec) {
+          hipLaunchKernelGGL((conv16f8_fwd_kernel<decltype(ksc)::value, decltype(ec)::value>), grid, block, lds, stream,
+                             x, w, bias, Y, g);
+        });
+      }) || !epi_ok)
+    return -2;
   return (int)hipGetLastError();
 }
 

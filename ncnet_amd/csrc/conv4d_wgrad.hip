@@ -17,6 +17,7 @@
 //     the (P,P) workgroups, which see every output tile exactly once.
 //   wgrad16v3 (the 16 -> 16 training layers): sliding G-plane ring, below.
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -963,12 +964,7 @@ static WGeom make_wgeom(int V, int I, int J, int K, int L, int KS, int ngroups) 
   return g;
 }
 
-#define KS_DISPATCH(M, ...) \
-  do { if (KS == 5) M(5, __VA_ARGS__); else if (KS == 3) M(3, __VA_ARGS__); \
-       else if (KS == 7) M(7, __VA_ARGS__); else if (KS == 1) M(1, __VA_ARGS__); else return -2; } while (0)
-
-// wgrad16v2.  part: [2 * ngroups][KS*KS (mode 0) or 1 (mode 2)][KS*KS][16 ci][16 co]
-// fp32 (one row per voxel-chunk half); partb: [2 * ngroups][16].
+// wgrad16v2<KS>, KS 5 / 3 / 7 / 1
 extern "C" int ncnet_wgrad16(const void* X, const void* G, float* part, float* partb, int V, int I, int J, int K,
                              int L, int KS, int ngroups, int dj_center, hipStream_t stream) {
   WGeom g = make_wgeom(V, I, J, K, L, KS, ngroups);
@@ -984,14 +980,14 @@ extern "C" int ncnet_wgrad16(const void* X, const void* G, float* part, float* p
   if (g.PR * g.RS * 32 > 65535) return -1;  // 16-bit voxel offset table
   size_t lds = (size_t)g.PR * g.RS * 32 + (size_t)nv32 * 32 + (size_t)nv32 * 2;
   dim3 block(512);
-#define WG2(KSV, _) hipLaunchKernelGGL((wgrad16v2_kernel<KSV>), grid, block, lds, stream, x, gg, part, partb, g)
-  KS_DISPATCH(WG2, 0);
-#undef WG2
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        hipLaunchKernelGGL((wgrad16v2_kernel<decltype(ksc)::value>), grid, block, lds, stream, x, gg, part, partb, g);
+      }))
+    return -2;
   return (int)hipGetLastError();
 }
 
-// wgrad16p (plane-only, whole-plane tiles: K, L <= 25): X [nsets][V,I,J,K,L,16]
-// (set stride xstride elements), G [NGG][...] (stride gstride); grid = ngroups * nsets.
+// wgrad16p<KS, NGG>, KS 5 / 3 / 7 / 1, NGG = ngg 1 or 2; grid = ngroups * nsets.
 extern "C" int ncnet_wgrad16p(const void* X, const void* G, float* part, float* partb, int V, int I, int J, int K,
                               int L, int KS, int ngroups, int nsets, int ngg, long long xstride, long long gstride,
                               hipStream_t stream) {
@@ -1007,36 +1003,34 @@ extern "C" int ncnet_wgrad16p(const void* X, const void* G, float* part, float* 
   if (lds > 160 * 1024) return -1;
   dim3 grid((unsigned)(ngroups * nsets)), block(512);
   const bf16* x = (const bf16*)X; const bf16* gg = (const bf16*)G;
-#define WGP(KSV, _) do { if (ngg == 2) hipLaunchKernelGGL((wgrad16p_kernel<KSV, 2>), grid, block, lds, stream, x, gg, part, partb, g, xstride, gstride, nsets); \
-                         else hipLaunchKernelGGL((wgrad16p_kernel<KSV, 1>), grid, block, lds, stream, x, gg, part, partb, g, xstride, gstride, nsets); } while (0)
-  KS_DISPATCH(WGP, 0);
-#undef WGP
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        dispatch_int<2, 1>(ngg, [&](auto nc) {   // ngg is 1 or 2 (checked above)
+          hipLaunchKernelGGL((wgrad16p_kernel<decltype(ksc)::value, decltype(nc)::value>), grid, block, lds, stream, x, gg,
+                             part, partb, g, xstride, gstride, nsets);
+        });
+      }))
+    return -2;
   return (int)hipGetLastError();
 }
 
-template <int KS, int T>
-static void w4_launch1(dim3 grid, dim3 block, hipStream_t stream, const bf16* x, const bf16* gg, float* part,
-                       float* partb, const W3Geom& g) {
-  using C = W4C<KS, T, T>;
-  const size_t lds = (size_t)C::LDS;
-  hipLaunchKernelGGL((wgrad16v4_kernel<KS, T, T>), grid, block, lds, stream, x, gg, part, partb, g);
-}
+// wgrad16v4 at the square K x K planes it is instantiated for (KS 5 / 3; K 30:
+// rows of 34 voxels, 2 DMAs); false (nothing launched) for any other shape.
 static bool w4_launch(int KS, int K, dim3 grid, dim3 block, hipStream_t stream, const bf16* x, const bf16* gg,
                       float* part, float* partb, const W3Geom& g) {
-  if (KS == 5 && K == 25) w4_launch1<5, 25>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 5 && K == 20) w4_launch1<5, 20>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 5 && K == 15) w4_launch1<5, 15>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 3 && K == 25) w4_launch1<3, 25>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 3 && K == 20) w4_launch1<3, 20>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 3 && K == 15) w4_launch1<3, 15>(grid, block, stream, x, gg, part, partb, g);
-  else if (KS == 5 && K == 30) w4_launch1<5, 30>(grid, block, stream, x, gg, part, partb, g);   // rows of 34 voxels: 2 DMAs
-  else if (KS == 3 && K == 30) w4_launch1<3, 30>(grid, block, stream, x, gg, part, partb, g);
-  else return false;
-  return true;
+  bool hit = false;
+  dispatch_int<5, 3>(KS, [&](auto ksc) {
+    hit = dispatch_int<25, 20, 15, 30>(K, [&](auto kc) {
+      constexpr int KSV = decltype(ksc)::value, T = decltype(kc)::value;
+      const size_t lds = (size_t)W4C<KSV, T, T>::LDS;
+      hipLaunchKernelGGL((wgrad16v4_kernel<KSV, T, T>), grid, block, lds, stream, x, gg, part, partb, g);
+    });
+  });
+  return hit;
 }
 
-// v3: ngroups column groups per dj (grid = ngroups * KS).
-// Tile rule (mirrored in ops/neigh_consensus.py wgrad_v3_groups):
+// Kernel selection: wgrad16v4 at its compile-time planes, else wgrad16v3<KS, NCH>
+// with NCH = VT / 64 voxel chunks per half.  grid = ngroups * KS.
+// Tile rule (mirrored in ops/nc/layers.py wgrad_v3_ntl):
 // ntl = ceil(K*L / 320), VT = roundup(ceil(K*L / ntl), 64).
 extern "C" int ncnet_wgrad16v3(const void* X, const void* G, float* part, float* partb, int V, int I, int J, int K,
                                int L, int KS, int ngroups, hipStream_t stream) {
@@ -1053,7 +1047,7 @@ extern "C" int ncnet_wgrad16v3(const void* X, const void* G, float* part, float*
   g.flags = tuning().wgrad_flags;
   if (g.VT > 384) return -1;                // <= 6 chunks per half
   // the wgrad_v3 A/B switch selects the general kernel only where it can stage the
-  // rows (RW <= 32); ops/neigh_consensus.py wgrad_v3_ntl mirrors the tile rule either way
+  // rows (RW <= 32); ops/nc/layers.py wgrad_v3_ntl mirrors the tile rule either way
   if (K == L && (!tuning().wgrad_v3 || g.RW > 32) &&
       w4_launch(KS, K, dim3((unsigned)(KS * ngroups)), dim3(512), stream, (const bf16*)X, (const bf16*)G, part,
                 partb, g))
@@ -1061,7 +1055,7 @@ extern "C" int ncnet_wgrad16v3(const void* X, const void* G, float* part, float*
   if (g.RW > 32) return -1;                 // v3: one wave-instruction per staged row
   // wgrad16v3<5, NCH> spills at NCH 3, 4, 6 (256 VGPRs of accumulators and
   // double-buffered fragments): split the plane into more, smaller tiles until
-  // the chunk count is 1, 2 or 5 (mirrored in ops/neigh_consensus.py wgrad_v3_ntl)
+  // the chunk count is 1, 2 or 5 (mirrored in ops/nc/layers.py wgrad_v3_ntl)
   if (KS == 5) {
     while (true) {
       const int nch = ((cdiv(KL, g.ntl) + 63) / 64);
@@ -1078,15 +1072,18 @@ extern "C" int ncnet_wgrad16v3(const void* X, const void* G, float* part, float*
   dim3 grid((unsigned)(KS * ngroups)), block(512);
   const bf16* x = (const bf16*)X; const bf16* gg = (const bf16*)G;
   const int nch = g.VT / 64;
-#define W3N(KSV, N) hipLaunchKernelGGL((wgrad16v3_kernel<KSV, N>), grid, block, lds, stream, x, gg, part, partb, g)
-#define W3(KSV) do { switch (nch) { case 1: W3N(KSV, 1); break; case 2: W3N(KSV, 2); break; case 3: W3N(KSV, 3); break; \
-                                    case 4: W3N(KSV, 4); break; case 5: W3N(KSV, 5); break; default: W3N(KSV, 6); } } while (0)
-  if (KS == 5) {
-    // only the spill-free chunk counts are instantiated (the tile rule above)
-    switch (nch) { case 1: W3N(5, 1); break; case 2: W3N(5, 2); break; case 5: W3N(5, 5); break; default: return -3; }
-  } else if (KS == 3) W3(3);
-  else return -2;
-#undef W3
-#undef W3N
+  auto launch = [&](auto ksc, auto nc) {
+    hipLaunchKernelGGL((wgrad16v3_kernel<decltype(ksc)::value, decltype(nc)::value>), grid, block, lds, stream, x, gg,
+                       part, partb, g);
+  };
+  bool nch_ok = false;
+  if (!dispatch_int<5, 3>(KS, [&](auto ksc) {
+        if constexpr (decltype(ksc)::value == 5)   // only the spill-free chunk counts are instantiated (the tile rule above)
+          nch_ok = dispatch_int<1, 2, 5>(nch, [&](auto nc) { launch(ksc, nc); });
+        else                                       // (VT <= 384 above: any other count is 6)
+          nch_ok = dispatch_int<1, 2, 3, 4, 5, 6>(nch >= 1 && nch <= 5 ? nch : 6, [&](auto nc) { launch(ksc, nc); });
+      }))
+    return -2;
+  if (!nch_ok) return -3;
   return (int)hipGetLastError();
 }

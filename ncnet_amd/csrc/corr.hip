@@ -16,6 +16,7 @@
 //   lib/model.py:177-191) when the feature rows are ordered in ks x ks spatial
 //   blocks: the full-resolution volume is never written.
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_fp8.h>
 
 namespace ncnet {
@@ -596,21 +597,22 @@ __global__ __launch_bounds__(512, 1) void corr_gemm_f8v2_kernel(GemmArgs p, int 
 
 using namespace ncnet;
 
-// y dtype: bf16 (fp8_scale == 0; ylo: optional low half) or OCP fp8 e4m3 scaled by fp8_scale.
-// y_f16: y is IEEE half (no lo half, no fp8).
 extern "C" int ncnet_l2norm_rows(const void* x, int x_is_bf16, void* y, float* inv_norm, int rows, int C,
                                  float fp8_scale, void* ylo, int y_f16, hipStream_t stream) {
   bf16* lo = (bf16*)ylo;
   dim3 grid((unsigned)cdiv(rows, 4)), block(256);
   const bool f8 = fp8_scale != 0.f;
   if (y_f16 && (f8 || lo)) return -1;
-#define L2N(TIN) do { \
-    if (f8) hipLaunchKernelGGL((l2norm_rows_kernel<TIN, 1>), grid, block, 0, stream, (const TIN*)x, y, inv_norm, rows, C, fp8_scale, nullptr); \
-    else if (y_f16) hipLaunchKernelGGL((l2norm_rows_kernel<TIN, 2>), grid, block, 0, stream, (const TIN*)x, y, inv_norm, rows, C, 1.f, nullptr); \
-    else hipLaunchKernelGGL((l2norm_rows_kernel<TIN, 0>), grid, block, 0, stream, (const TIN*)x, y, inv_norm, rows, C, 1.f, lo); \
-  } while (0)
-  if (x_is_bf16) L2N(bf16); else L2N(float);
-#undef L2N
+  // l2norm_rows_kernel<TIN, OUT>: OUT 1 fp8 (scaled), 2 IEEE half, 0 bf16 (+ lo half)
+  auto launch = [&](auto* xt) {
+    using TIN = std::remove_pointer_t<decltype(xt)>;
+    dispatch_int<1, 2, 0>(f8 ? 1 : y_f16 ? 2 : 0, [&](auto oc) {
+      constexpr int OUT = decltype(oc)::value;
+      hipLaunchKernelGGL((l2norm_rows_kernel<TIN, OUT>), grid, block, 0, stream, (const TIN*)x, y, inv_norm, rows, C,
+                         OUT == 1 ? fp8_scale : 1.f, OUT == 0 ? lo : nullptr);
+    });
+  };
+  if (x_is_bf16) launch((bf16*)nullptr); else launch((float*)nullptr);
   return (int)hipGetLastError();
 }
 
@@ -637,9 +639,11 @@ static int cg2_stages() {
   return tuning().corr_ns == 4 ? 4 : 3;
 }
 
-// C[b] = A[amap[b]] . B[bmap[b]]^T ; out_bf16 selects the output dtype.
-// fp8_out_scale != 0: A, B are OCP fp8 e4m3 and C = fp8_out_scale * (A . B^T).
-// f16: A, B (and a 16-bit C) are IEEE half.
+// operand type of the v1 kernel, corr_gemm_kernel<.., F8, F16>: 1 fp8, 2 IEEE half, 0 bf16
+static int operand_mode(bool f8, int f16) { return f8 ? 1 : f16 ? 2 : 0; }
+
+// Kernel selection: fp8 on the persistent f8v2 ring, bf16 / f16 on the v2 ring
+// (both where use_v2 allows), else the v1 kernel for all three operand types.
 extern "C" int ncnet_corr_gemm(const void* A, const void* B, void* C, const int* amap, const int* bmap, int batch,
                                int M, int N, int K, long long sA, long long sB, long long sC, int out_bf16,
                                float fp8_out_scale, int f16, hipStream_t stream) {
@@ -655,42 +659,38 @@ extern "C" int ncnet_corr_gemm(const void* A, const void* B, void* C, const int*
     const int tiles = batch * p.tiles_m * p.tiles_n;
     dim3 grid((unsigned)std::min(tiles, device_num_cus())), block(512);   // persistent
     const size_t lds = cf2::NS * cf2::STAGE;
-    if (out_bf16) hipLaunchKernelGGL((corr_gemm_f8v2_kernel<true, false>), grid, block, lds, stream, p, tiles);
-    else hipLaunchKernelGGL((corr_gemm_f8v2_kernel<false, false>), grid, block, lds, stream, p, tiles);
+    dispatch_bool(out_bf16 != 0, [&](auto ob) {
+      hipLaunchKernelGGL((corr_gemm_f8v2_kernel<decltype(ob)::value, false>), grid, block, lds, stream, p, tiles);
+    });
     return (int)hipGetLastError();
   }
-  if (use_v2(f8, batch, M, N, K)) {
+  if (use_v2(f8, batch, M, N, K)) {   // bf16 / f16 (fp8 took the branch above)
     p.tiles_m = cdiv(M, cg2::BM); p.tiles_n = cdiv(N, cg2::BN);
     dim3 grid((unsigned)(batch * p.tiles_m * p.tiles_n)), block(512);
-#define CG2(OB, NSV, H) hipLaunchKernelGGL((corr_gemm_v2_kernel<OB, false, NSV, H>), grid, block, NSV * cg2::STAGE, stream, p)
-    if (cg2_stages() == 3) {
-      if (f16) { if (out_bf16) CG2(true, 3, true); else CG2(false, 3, true); }
-      else { if (out_bf16) CG2(true, 3, false); else CG2(false, 3, false); }
-    } else {
-      if (f16) { if (out_bf16) CG2(true, 4, true); else CG2(false, 4, true); }
-      else { if (out_bf16) CG2(true, 4, false); else CG2(false, 4, false); }
-    }
-#undef CG2
+    dispatch_int<3, 4>(cg2_stages(), [&](auto nsc) {   // cg2_stages() is 3 or 4
+      constexpr int NS = decltype(nsc)::value;
+      dispatch_bool(f16 != 0, [&](auto hc) {
+        dispatch_bool(out_bf16 != 0, [&](auto ob) {
+          hipLaunchKernelGGL((corr_gemm_v2_kernel<decltype(ob)::value, false, NS, decltype(hc)::value>), grid, block,
+                             NS * cg2::STAGE, stream, p);
+        });
+      });
+    });
     return (int)hipGetLastError();
   }
   p.tiles_m = cdiv(M, BM); p.tiles_n = cdiv(N, BN);
   dim3 grid((unsigned)(batch * p.tiles_m * p.tiles_n)), block(256);
   size_t lds = (size_t)(BM + BN) * 128;
-  if (f8) {
-    if (out_bf16) hipLaunchKernelGGL((corr_gemm_kernel<true, false, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((corr_gemm_kernel<false, false, true>), grid, block, lds, stream, p);
-  } else if (f16) {
-    if (out_bf16) hipLaunchKernelGGL((corr_gemm_kernel<true, false, false, true>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((corr_gemm_kernel<false, false, false, true>), grid, block, lds, stream, p);
-  } else {
-    if (out_bf16) hipLaunchKernelGGL((corr_gemm_kernel<true, false, false>), grid, block, lds, stream, p);
-    else hipLaunchKernelGGL((corr_gemm_kernel<false, false, false>), grid, block, lds, stream, p);
-  }
+  dispatch_int<1, 2, 0>(operand_mode(f8, f16), [&](auto mc) {
+    constexpr int MODE = decltype(mc)::value;
+    dispatch_bool(out_bf16 != 0, [&](auto ob) {
+      hipLaunchKernelGGL((corr_gemm_kernel<decltype(ob)::value, false, MODE == 1, MODE == 2>), grid, block, lds, stream, p);
+    });
+  });
   return (int)hipGetLastError();
 }
 
-// Fused correlation + 2x2x2x2 max-pool.  A rows / B rows must be in
-// 2x2-block order (see ncnet_block_order_rows); hA, wA, hB, wB even.
+// The same selection with the POOL epilogue (fp32 pooled values + codes only).
 extern "C" int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_val, uint8_t* pool_idx, int batch,
                                      int hA, int wA, int hB, int wB, int K, long long sA, long long sB,
                                      float fp8_out_scale, int f16, hipStream_t stream) {
@@ -713,20 +713,21 @@ extern "C" int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_v
   if (use_v2(f8, batch, p.M, p.N, K)) {
     p.tiles_m = cdiv(p.M, cg2::BM); p.tiles_n = cdiv(p.N, cg2::BN);
     dim3 grid((unsigned)(batch * p.tiles_m * p.tiles_n)), block(512);
-    if (f16) {
-      if (cg2_stages() == 3) hipLaunchKernelGGL((corr_gemm_v2_kernel<false, true, 3, true>), grid, block, 3 * cg2::STAGE, stream, p);
-      else hipLaunchKernelGGL((corr_gemm_v2_kernel<false, true, 4, true>), grid, block, 4 * cg2::STAGE, stream, p);
-    } else {
-      if (cg2_stages() == 3) hipLaunchKernelGGL((corr_gemm_v2_kernel<false, true, 3>), grid, block, 3 * cg2::STAGE, stream, p);
-      else hipLaunchKernelGGL((corr_gemm_v2_kernel<false, true, 4>), grid, block, 4 * cg2::STAGE, stream, p);
-    }
+    dispatch_int<3, 4>(cg2_stages(), [&](auto nsc) {   // cg2_stages() is 3 or 4
+      constexpr int NS = decltype(nsc)::value;
+      dispatch_bool(f16 != 0, [&](auto hc) {
+        hipLaunchKernelGGL((corr_gemm_v2_kernel<false, true, NS, decltype(hc)::value>), grid, block, NS * cg2::STAGE,
+                           stream, p);
+      });
+    });
     return (int)hipGetLastError();
   }
   p.tiles_m = cdiv(p.M, BM); p.tiles_n = cdiv(p.N, BN);
   dim3 grid((unsigned)(batch * p.tiles_m * p.tiles_n)), block(256);
   size_t lds = (size_t)(BM + BN) * 128;
-  if (f8) hipLaunchKernelGGL((corr_gemm_kernel<false, true, true>), grid, block, lds, stream, p);
-  else if (f16) hipLaunchKernelGGL((corr_gemm_kernel<false, true, false, true>), grid, block, lds, stream, p);
-  else hipLaunchKernelGGL((corr_gemm_kernel<false, true, false>), grid, block, lds, stream, p);
+  dispatch_int<1, 2, 0>(operand_mode(f8, f16), [&](auto mc) {
+    constexpr int MODE = decltype(mc)::value;
+    hipLaunchKernelGGL((corr_gemm_kernel<false, true, MODE == 1, MODE == 2>), grid, block, lds, stream, p);
+  });
   return (int)hipGetLastError();
 }

@@ -36,6 +36,7 @@
 // Layouts: X bf16 [V,I,J,K,L,16]; Wt bf16 [KS*KS (di,dj)][64 lanes][8] =
 // the A fragments (lane l: tap row l & 31, ci 8 (l >> 5) + e); Y fp32 [V,I,J,K,L].
 #include "common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace ncnet {
@@ -294,9 +295,7 @@ using namespace ncnet;
 #define C1_RJ 3
 #endif
 
-// Y fp32 [V,I,J,K,L] = act(bias + conv(X, W)) for a 16 -> 1 layer; Wt: the tap-row
-// A fragments (ops/packing.py cout1_taps_weights).  Returns -1 for shapes
-// without an instantiation (the caller keeps the output-plane-block kernel).
+// one instantiation: KS 5 at the 25 x 25 (400 px) training planes
 extern "C" int ncnet_cout1_taps_fwd(const void* X, const void* Wt, const float* bias, float* Y, int V, int I, int J,
                                     int K, int L, int KS, int relu, hipStream_t s) {
   if (!(KS == 5 && K == 25 && L == 25)) return -1;

@@ -13,6 +13,7 @@
 // four HWC neighbours (3 contiguous bytes each) and writes the 3 normalised
 // channels of out[b, :, y, x] (fp32, NCHW, what the trunk consumes).
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 

@@ -7,6 +7,7 @@
 //
 //   Y[r, c] = act(Y[r, c] + b[c])          (bf16 rows of C channels, fp32 bias)
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 
@@ -224,17 +225,15 @@ extern "C" int ncnet_bias_act(void* Y, const float* b, long long rows, int C, in
   if (n8 == 0) return 0;
   dim3 grid((unsigned)((n8 + 255) / 256)), block(256);
   uint16_t* y = (uint16_t*)Y;
-  if (f16) {
-    if (relu) hipLaunchKernelGGL((bias_act_kernel<true, true>), grid, block, 0, stream, y, b, n8, C / 8);
-    else hipLaunchKernelGGL((bias_act_kernel<false, true>), grid, block, 0, stream, y, b, n8, C / 8);
-  } else {
-    if (relu) hipLaunchKernelGGL((bias_act_kernel<true, false>), grid, block, 0, stream, y, b, n8, C / 8);
-    else hipLaunchKernelGGL((bias_act_kernel<false, false>), grid, block, 0, stream, y, b, n8, C / 8);
-  }
+  dispatch_bool(relu != 0, [&](auto rc) {
+    dispatch_bool(f16 != 0, [&](auto hc) {
+      hipLaunchKernelGGL((bias_act_kernel<decltype(rc)::value, decltype(hc)::value>), grid, block, 0, stream, y, b, n8,
+                         C / 8);
+    });
+  });
   return (int)hipGetLastError();
 }
 
-// X [N, H, W, C] (NHWC, 16-bit), Y [N, Ho, Wo, C]; b fp32 [C]; C % 8 == 0.
 extern "C" int ncnet_maxpool_bias_act(const void* X, void* Y, const float* b, int N, int H, int W, int C, int Ho,
                                       int Wo, int k, int stride, int pad, int relu, int f16, hipStream_t stream) {
   if (C % 8 || k < 1 || stride < 1 || pad < 0 || 2 * pad > k) return -1;
@@ -242,12 +241,12 @@ extern "C" int ncnet_maxpool_bias_act(const void* X, void* Y, const float* b, in
   if (total == 0) return 0;
   dim3 grid((unsigned)((total + 255) / 256)), block(256);
   const uint16_t* x = (const uint16_t*)X; uint16_t* y = (uint16_t*)Y;
-#define MPB(R, H) hipLaunchKernelGGL((maxpool_bias_act_kernel<R, H>), grid, block, 0, stream, x, y, b, N, H_, W, C / 8, Ho, \
-                                     Wo, k, stride, pad)
-  const int H_ = H;
-  if (f16) { if (relu) MPB(true, true); else MPB(false, true); }
-  else { if (relu) MPB(true, false); else MPB(false, false); }
-#undef MPB
+  dispatch_bool(relu != 0, [&](auto rc) {
+    dispatch_bool(f16 != 0, [&](auto hc) {
+      hipLaunchKernelGGL((maxpool_bias_act_kernel<decltype(rc)::value, decltype(hc)::value>), grid, block, 0, stream, x,
+                         y, b, N, H, W, C / 8, Ho, Wo, k, stride, pad);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -301,7 +300,7 @@ extern "C" int ncnet_gather_bf16(const float* src, const int* idx, void* out, lo
 //   dst_s[map_s(j)] = sum_{r < R_s} src_s[r * N_s + j]
 // map = idx_s[j] (a layout permutation; < 0 drops the column) or j (idx null);
 // the weight-gradient partials of the NeighConsensus layers reduced and laid
-// out in the checkpoint layout in one launch (ops/neigh_consensus.py
+// out in the checkpoint layout in one launch (ops/nc/layers.py
 // reduce_partials).  A block owns 64 column quads; its 4 row slices sum rows
 // r = slice (mod 4) and are combined in a fixed order through LDS, so the
 // result is the same on every run.

@@ -17,6 +17,7 @@
 // shape, else the heuristic's first.  One workspace per device.
 #include <hip/hip_runtime.h>
 #include <hipblaslt/hipblaslt.h>
+#include "launchers.h"
 
 #include <map>
 #include <tuple>
@@ -110,9 +111,6 @@ int run(LtDev& d, LtPlan& p, int i, const void* W, const void* X, const void* R,
 
 }  // namespace
 
-// Y = act(X W^T + bias + R); returns 0, or a negative code.  tune != 0: time
-// every heuristic candidate once for this shape (not while the stream is
-// being captured) and keep the fastest.
 extern "C" int ncnet_gemm_lt(const void* X, const void* W, const float* bias, const void* R, void* Y, int m, int cin,
                              int cout, int relu, int f16, int tune, hipStream_t st) {
   LtDev* d = nullptr;

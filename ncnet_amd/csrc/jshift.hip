@@ -14,6 +14,7 @@
 // all run on the conv16 / wgrad16 MFMA kernels (lib/conv4d.py:11-51 semantics).
 // The exact weight maps are verified on CPU (tests/test_kernel_emulation.py).
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_fp8.h>
 #include <stdlib.h>
 
@@ -98,19 +99,24 @@ __global__ __launch_bounds__(256) void ijsum_kernel(const float* __restrict__ Z,
 
 using namespace ncnet;
 
-#define KS_DISPATCH(M, ...) \
-  do { if (KS == 5) M(5, __VA_ARGS__); else if (KS == 3) M(3, __VA_ARGS__); \
-       else if (KS == 7) M(7, __VA_ARGS__); else if (KS == 1) M(1, __VA_ARGS__); else return -1; } while (0)
-
-// S bf16 (non-temporal stores: the >= 1.6 GB output never stays in L2) or OCP fp8 e4m3 (inference).
+// ijpack_kernel<T, KS, FP8, NT>: fp8 S (inference), or bf16 S with non-temporal
+// stores (the >= 1.6 GB output never stays in L2).  An unsupported KS is -1 here.
 extern "C" int ncnet_ijpack(const void* X, int x_is_bf16, void* S, int V, int I, int J, int K, int L, int KS, int sgn,
                             int s_fp8, hipStream_t stream) {
   long long nvox = (long long)V * I * J * K * L;
   dim3 grid((unsigned)(V * I * J), (unsigned)((K * L + 255) / 256));
-#define IJP(KSV, T) do { if (s_fp8) hipLaunchKernelGGL((ijpack_kernel<T, KSV, true>), grid, dim3(256), 0, stream, (const T*)X, S, nvox, I, J, K * L, sgn); \
-                         else hipLaunchKernelGGL((ijpack_kernel<T, KSV, false, true>), grid, dim3(256), 0, stream, (const T*)X, S, nvox, I, J, K * L, sgn); } while (0)
-  if (x_is_bf16) KS_DISPATCH(IJP, bf16); else KS_DISPATCH(IJP, float);
-#undef IJP
+  auto launch = [&](auto ksc, auto* xt) {
+    using T = std::remove_pointer_t<decltype(xt)>;
+    dispatch_bool(s_fp8 != 0, [&](auto f8) {
+      constexpr bool F8 = decltype(f8)::value;   // bf16 S: non-temporal stores
+      hipLaunchKernelGGL((ijpack_kernel<T, decltype(ksc)::value, F8, !F8>), grid, dim3(256), 0, stream, (const T*)X, S,
+                         nvox, I, J, K * L, sgn);
+    });
+  };
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        if (x_is_bf16) launch(ksc, (bf16*)nullptr); else launch(ksc, (float*)nullptr);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }
 
@@ -118,8 +124,10 @@ extern "C" int ncnet_ijsum(const float* Z, const float* bias, float* y, int V, i
                            int relu, int sgn, hipStream_t stream) {
   long long nvox = (long long)V * I * J * K * L;
   dim3 grid((unsigned)(V * I * J), (unsigned)((K * L + 255) / 256));
-#define IJS(KSV, _) hipLaunchKernelGGL((ijsum_kernel<KSV>), grid, dim3(256), 0, stream, Z, bias, y, nvox, I, J, K * L, relu, sgn)
-  KS_DISPATCH(IJS, 0);
-#undef IJS
+  if (!dispatch_int<5, 3, 7, 1>(KS, [&](auto ksc) {
+        hipLaunchKernelGGL((ijsum_kernel<decltype(ksc)::value>), grid, dim3(256), 0, stream, Z, bias, y, nvox, I, J,
+                           K * L, relu, sgn);
+      }))
+    return -1;
   return (int)hipGetLastError();
 }

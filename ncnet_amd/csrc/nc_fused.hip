@@ -33,6 +33,7 @@
 // needs no atomics and no barriers; two barriers per hidden plane order the
 // S and h buffers.
 #include "common.h"
+#include "launchers.h"
 #include <stdlib.h>
 
 namespace ncnet {
@@ -648,9 +649,10 @@ __global__ __launch_bounds__(512, 4) void nc_fused_k3_f8_kernel(const bf16* __re
 
 using namespace ncnet;
 
-// x0 bf16 [V,I,J,K,L]; W1p / W2p bf16 [5][64][8] (pack_w16_planes of the ij layer weights);
-// b1 fp32 [16], b2 fp32 [1]; y fp32 [V,I,J,K,L].
-// f16: x0 / W1p / W2p are IEEE half (f16 MFMA, f16 hidden activation).
+// compile-time geometry of a fused kernel: tile (TK, TL), R planes per workgroup (0: all runtime), NW waves
+template <int TK_, int TL_, int R_, int NW_>
+struct NcfTile { static constexpr int TK = TK_, TL = TL_, R = R_, NW = NW_; };
+
 extern "C" int ncnet_nc_fused_k3(const void* X, const void* W1p, const float* b1, const void* W2p, const float* b2,
                                  float* Y, int V, int I, int J, int K, int L, int R, int IR, int TK, int TL, int f16,
                                  hipStream_t stream) {
@@ -671,27 +673,25 @@ extern "C" int ncnet_nc_fused_k3(const void* X, const void* W1p, const float* b1
     return -2;
   if (lds > 160 * 1024) return -3;
   dim3 grid((unsigned)((size_t)V * g.nib * g.njb * g.nkt * g.nlt)), block(nw * 64);
-#define NCF(H, A, B, C, W) hipLaunchKernelGGL((nc_fused_k3_kernel<H, A, B, C, W>), grid, block, lds, stream, (const bf16*)X, \
-                                              (const u32x4*)W1p, b1, (const u32x4*)W2p, b2, Y, g)
-  // the tiles ops/neigh_consensus.py fused_tiles picks at 3200 px (75x100 planes)
+  // the tiles ops/nc/fused.py fused_tiles picks at 3200 px (75x100 planes)
   // and 1600 px (37x50) get compile-time geometry; anything else the runtime one
   const bool t3200 = TK == 15 && TL == 20 && R == 10, t1600 = TK == 19 && TL == 17 && R == 8;
   const bool t3200b = big && TK == 15 && TL == 20 && R == 20;
-  if (f16) {
-    if (t3200b) NCF(true, 15, 20, 20, 16); else if (big) NCF(true, 0, 0, 0, 16);
-    else if (t3200) NCF(true, 15, 20, 10, 8); else if (t1600) NCF(true, 19, 17, 8, 8); else NCF(true, 0, 0, 0, 8);
-  } else {
-    if (t3200b) NCF(false, 15, 20, 20, 16); else if (big) NCF(false, 0, 0, 0, 16);
-    else if (t3200) NCF(false, 15, 20, 10, 8); else if (t1600) NCF(false, 19, 17, 8, 8); else NCF(false, 0, 0, 0, 8);
-  }
-#undef NCF
+  dispatch_bool(f16 != 0, [&](auto hc) {
+    auto launch = [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((nc_fused_k3_kernel<decltype(hc)::value, T::TK, T::TL, T::R, T::NW>), grid, block, lds, stream,
+                         (const bf16*)X, (const u32x4*)W1p, b1, (const u32x4*)W2p, b2, Y, g);
+    };
+    if (t3200b) launch(NcfTile<15, 20, 20, 16>{});
+    else if (big) launch(NcfTile<0, 0, 0, 16>{});
+    else if (t3200) launch(NcfTile<15, 20, 10, 8>{});
+    else if (t1600) launch(NcfTile<19, 17, 8, 8>{});
+    else launch(NcfTile<0, 0, 0, 8>{});
+  });
   return (int)hipGetLastError();
 }
 
-// fp8 fused stack: x0 bf16 [V,I,J,K,L]; W1a / W2a [64] x 32 B MX fragments of
-// taps 0..7, W1b / W2b [64] x 8 B fragments of tap 8 (e4m3, weights * sw);
-// b1 fp32 [16], b2 fp32 [1]; y fp32.  Scales: sx (x0), inv1 = 1 / (sw1 sx),
-// sh (hidden), inv2 = 1 / (sw2 sh).
 extern "C" int ncnet_nc_fused_k3_f8(const void* X, const void* W1a, const void* W1b, const float* b1, const void* W2a,
                                     const void* W2b, const float* b2, float* Y, int V, int I, int J, int K, int L, int R,
                                     int IR, int TK, int TL, float sx, float inv1, float sh, float inv2,
@@ -709,13 +709,15 @@ extern "C" int ncnet_nc_fused_k3_f8(const void* X, const void* W1a, const void* 
   if (lds > 80 * 1024) return -3;
   NCF8Scales sc{sx, inv1, sh, inv2};
   dim3 grid((unsigned)((size_t)V * g.nib * g.njb * g.nkt * g.nlt)), block(512);
-#define NCF8(A, B, C) hipLaunchKernelGGL((nc_fused_k3_f8_kernel<A, B, C>), grid, block, lds, stream, (const bf16*)X, \
-                                         (const i32x8*)W1a, (const long*)W1b, b1, (const i32x8*)W2a, (const long*)W2b, b2, Y, g, sc)
-  // ops/neigh_consensus.py runs the bf16 kernel's tiling (fused_tiles): the
+  auto launch = [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((nc_fused_k3_f8_kernel<T::TK, T::TL, T::R>), grid, block, lds, stream, (const bf16*)X,
+                       (const i32x8*)W1a, (const long*)W1b, b1, (const i32x8*)W2a, (const long*)W2b, b2, Y, g, sc);
+  };
+  // ops/nc/fused.py runs the bf16 kernel's tiling (fused_tiles): the
   // 3200 px and 1600 px tiles get compile-time geometry
-  if (TK == 15 && TL == 20 && R == 10) NCF8(15, 20, 10);
-  else if (TK == 19 && TL == 17 && R == 8) NCF8(19, 17, 8);
-  else NCF8(0, 0, 0);
-#undef NCF8
+  if (TK == 15 && TL == 20 && R == 10) launch(NcfTile<15, 20, 10, 8>{});
+  else if (TK == 19 && TL == 17 && R == 8) launch(NcfTile<19, 17, 8, 8>{});
+  else launch(NcfTile<0, 0, 0, 8>{});
   return (int)hipGetLastError();
 }

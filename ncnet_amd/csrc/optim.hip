@@ -17,6 +17,7 @@
 // data parallelism the count runs AFTER the gradient all-reduce: a NaN on any
 // rank reaches every rank's sum, so all ranks skip the same step.
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 

@@ -27,6 +27,7 @@
 // need = log(1 - confidence) / log(1 - w^3) is re-evaluated.  The number of
 // rounds is bounded by ceil(max_iters / 256), fixed at launch.
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 namespace pnp {
@@ -559,9 +560,6 @@ extern "C" int ncnet_p3p_solve(const double* rays, const double* X, int M, doubl
   return (int)hipGetLastError();
 }
 
-// rays / X [N, 3] fp64, offsets [B + 1] int32, keys [B] int64; P [B, 3, 4] fp64,
-// ninl [B] int32, mask [N] uint8 (zeroed by the caller), list [N] int32 workspace,
-// rounds [B] int32 or null.  cos_thr = cos(thr_rad), 0 < thr_rad < pi / 2.
 extern "C" int ncnet_p3p_ransac_batch(const double* rays, const double* X, const int* offsets, const long long* keys,
                                       int B, long long N, double cos_thr, int max_iters, double confidence,
                                       int lo_iters, double* P, int* ninl, uint8_t* mask, int* list, int* rounds,

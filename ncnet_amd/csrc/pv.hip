@@ -34,6 +34,7 @@
 // Every loop's trip count is fixed by the launch arguments (points, poses);
 // none depends on the data.
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 namespace pv {
@@ -165,9 +166,6 @@ using namespace ncnet::pv;
 
 extern "C" int ncnet_pv_pmax() { return PMAX; }
 
-// xyz [N, 3] fp64, rgb [N, 3] fp32, KP [C, 3, 4] fp64 with C <= PMAX;
-// zbuf [C, h * w] u64 preset to the bits of +inf, winner [C, h * w] int32 preset to -1;
-// synth [C, h, w, 3] fp32, flag [C, h, w] bytes.  C * h * w < 2^31, N < 2^31.
 extern "C" int ncnet_pv_render(const double* xyz, const float* rgb, long long N, const double* KP, int C, int h, int w,
                                unsigned long long* zbuf, int* winner, float* synth, uint8_t* flag,
                                hipStream_t stream) {
@@ -185,7 +183,6 @@ extern "C" int ncnet_pv_render(const double* xyz, const float* rgb, long long N,
   return (int)hipGetLastError();
 }
 
-// oq / os [B, 8, H, W] fp32, flag [B, H, W] bytes, err [B, ny * nx] fp32
 extern "C" int ncnet_pv_desc_err(const float* oq, const float* os, const uint8_t* flag, int B, int H, int W, int ny,
                                  int nx, float* err, hipStream_t stream) {
   const long long items = (long long)B * ny * nx;

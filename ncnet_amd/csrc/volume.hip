@@ -16,6 +16,7 @@
 //    'softmax', 'l1' and None normalisations (train.py:111-116).
 //  * maxpool4d: stride = kernel = ks 4D max pool + packed 2-bit offsets.
 #include "common.h"
+#include "launchers.h"
 
 namespace ncnet {
 
@@ -727,17 +728,15 @@ __global__ __launch_bounds__(256) void transpose_kernel(const T* __restrict__ x,
 
 using namespace ncnet;
 
-extern "C" int ncnet_pad_geom(int K, int L, int KS, int* lp, int* ppl);   // csrc/conv1x.hip
 static unsigned tiles64(int V, int R, int C) { return (unsigned)((long long)V * cdiv(R, 64) * cdiv(C, 64)); }
 
-// sum_kind: 1 sum exp(x - max), 2 plain sum (only when se != nullptr)
+// The launchers' contracts are in launchers.h.
 extern "C" int ncnet_stats_rows(const float* x, float* mx, int* arg, float* se, long long rows, int C, int sum_kind,
                                 hipStream_t s) {
   hipLaunchKernelGGL(stats_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, mx, arg, se, rows, C,
                      sum_kind);
   return (int)hipGetLastError();
 }
-// work: nullptr (nchunk = 1) or 3 * V * nchunk * C floats of partials.
 extern "C" int ncnet_stats_cols(const float* x, float* mx, int* arg, float* se, int V, int R, int C, float* work,
                                 int nchunk, int sum_kind, hipStream_t s) {
   if (nchunk <= 1 || work == nullptr) {
@@ -753,8 +752,6 @@ extern "C" int ncnet_stats_cols(const float* x, float* mx, int* arg, float* se, 
                      se ? ps : nullptr, mx, arg, se, V, C, nchunk, sum_kind);
   return (int)hipGetLastError();
 }
-// stats2d: work = 3 * V * (nct * R + nrt * C) floats of partials (nrt = ceil(R / 64), nct = ceil(C / 256)).
-// sum_kind 0: max / argmax only (rse, cse ignored).
 extern "C" int ncnet_stats2d(const float* x, float* rmx, int* rarg, float* rse, float* cmx, int* carg, float* cse,
                              int V, int R, int C, float* work, int sum_kind, hipStream_t s) {
   const bool vec = C % 4 == 0;   // 16-byte rows: one float4 per lane and row; else four scalar loads
@@ -766,20 +763,20 @@ extern "C" int ncnet_stats2d(const float* x, float* rmx, int* rarg, float* rse, 
   float* rpm = work; int* rpi = (int*)(work + nr); float* rps = work + 2 * nr;
   float* cpm = work + 3 * nr; int* cpi = (int*)(cpm + nc); float* cps = cpm + 2 * nc;
   const dim3 grid((unsigned)((size_t)V * nrt * nct)), blk(256);
-#define S2D_TILE(WSV, VECV) do { \
-    if (rt == 4) hipLaunchKernelGGL((stats2d_tile_kernel<WSV, VECV, 4>), grid, blk, 0, s, x, R, C, nrt, nct, rpm, rpi, rps, cpm, cpi, cps); \
-    else if (rt == 2) hipLaunchKernelGGL((stats2d_tile_kernel<WSV, VECV, 2>), grid, blk, 0, s, x, R, C, nrt, nct, rpm, rpi, rps, cpm, cpi, cps); \
-    else hipLaunchKernelGGL((stats2d_tile_kernel<WSV, VECV, 1>), grid, blk, 0, s, x, R, C, nrt, nct, rpm, rpi, rps, cpm, cpi, cps); \
-  } while (0)
-#define S2D(WSV) do { \
-    if (vec) S2D_TILE(WSV, true); \
-    else S2D_TILE(WSV, false); \
-    hipLaunchKernelGGL(stats2d_merge_kernel<WSV>, dim3((unsigned)cdiv(4 * V * R, 256)), blk, 0, s, rpm, rpi, rps, rmx, rarg, rse, V, R, nct); \
-    hipLaunchKernelGGL(stats2d_merge_kernel<WSV>, dim3((unsigned)cdiv(4 * V * C, 256)), blk, 0, s, cpm, cpi, cps, cmx, carg, cse, V, C, nrt); \
-  } while (0)
-  if (sum_kind == 1) S2D(1); else if (sum_kind == 2) S2D(2); else S2D(0);
-#undef S2D
-#undef S2D_TILE
+  // stats2d_tile_kernel<WS = sum kind, VEC, RT> then stats2d_merge_kernel<WS> for the rows and the columns
+  dispatch_int<1, 2, 0>(sum_kind == 1 || sum_kind == 2 ? sum_kind : 0, [&](auto wsc) {
+    constexpr int WS = decltype(wsc)::value;
+    dispatch_bool(vec, [&](auto vc) {
+      dispatch_int<4, 2, 1>(rt, [&](auto rtc) {   // rt is 4, 2 or 1 (above)
+        hipLaunchKernelGGL((stats2d_tile_kernel<WS, decltype(vc)::value, decltype(rtc)::value>), grid, blk, 0, s, x, R, C,
+                           nrt, nct, rpm, rpi, rps, cpm, cpi, cps);
+      });
+    });
+    hipLaunchKernelGGL(stats2d_merge_kernel<WS>, dim3((unsigned)cdiv(4 * V * R, 256)), blk, 0, s, rpm, rpi, rps, rmx, rarg,
+                       rse, V, R, nct);
+    hipLaunchKernelGGL(stats2d_merge_kernel<WS>, dim3((unsigned)cdiv(4 * V * C, 256)), blk, 0, s, cpm, cpi, cps, cmx, carg,
+                       cse, V, C, nrt);
+  });
   return (int)hipGetLastError();
 }
 extern "C" int ncnet_match_candidates(const float* cmx, const float* cse, const int* carg, const float* rmx,
@@ -790,7 +787,6 @@ extern "C" int ncnet_match_candidates(const float* cmx, const float* cse, const 
                      rarg, code, fs1, fs2, fs3, fs4, k, m, sc, key);
   return (int)hipGetLastError();
 }
-// pad_ks > 0: out_x / out_xt are padded bf16 planes for kernel size pad_ks (I2 x J2 = R, K2 x L2 = C)
 extern "C" int ncnet_mm_apply(const float* c, const float* rmax, const float* cmax, float* out_f32, void* out_x,
                               void* out_xt, int V, int R, int C, float eps, int x_f16, int pad_ks, int I2, int J2,
                               int K2, int L2, hipStream_t s) {
@@ -798,18 +794,16 @@ extern "C" int ncnet_mm_apply(const float* c, const float* rmax, const float* cm
   if (pad_ks > 0) {
     if (x_f16 || I2 * J2 != R || K2 * L2 != C || I2 != K2 || J2 != L2) return -1;
     pg.P = pad_ks / 2;
-    ncnet_pad_geom(K2, L2, pad_ks, &pg.LP, &pg.PPL);
-    hipLaunchKernelGGL((mm_apply_kernel<false, true>), dim3(tiles64(V, R, C)), dim3(256), 0, s, c, rmax, cmax, out_f32,
-                       (uint16_t*)out_x, (uint16_t*)out_xt, R, C, eps, pg);
-  } else if (x_f16)
-    hipLaunchKernelGGL((mm_apply_kernel<true, false>), dim3(tiles64(V, R, C)), dim3(256), 0, s, c, rmax, cmax, out_f32,
-                       (uint16_t*)out_x, (uint16_t*)out_xt, R, C, eps, pg);
-  else
-    hipLaunchKernelGGL((mm_apply_kernel<false, false>), dim3(tiles64(V, R, C)), dim3(256), 0, s, c, rmax, cmax, out_f32,
-                       (uint16_t*)out_x, (uint16_t*)out_xt, R, C, eps, pg);
+    ncnet_pad_geom(K2, L2, pad_ks, &pg.LP, &pg.PPL);   // csrc/conv1x.hip
+  }
+  // mm_apply_kernel<F16, PAD>: padded planes (bf16 only), else f16 or bf16 matrices
+  dispatch_int<2, 1, 0>(pad_ks > 0 ? 2 : x_f16 ? 1 : 0, [&](auto mc) {
+    constexpr int MODE = decltype(mc)::value;
+    hipLaunchKernelGGL((mm_apply_kernel<MODE == 1, MODE == 2>), dim3(tiles64(V, R, C)), dim3(256), 0, s, c, rmax, cmax,
+                       out_f32, (uint16_t*)out_x, (uint16_t*)out_xt, R, C, eps, pg);
+  });
   return (int)hipGetLastError();
 }
-// work: nullptr (separate row / column passes) or V * (ceil(C/256) * R + ceil(R/64) * C) floats (one pass)
 extern "C" int ncnet_mm_bwd(const float* c, const float* g, const float* rmax, const int* rarg, const float* cmax,
                             const int* carg, float* rsum, float* csum, float* gc, int V, int R, int C, float eps,
                             float* work, hipStream_t s) {
@@ -819,10 +813,10 @@ extern "C" int ncnet_mm_bwd(const float* c, const float* g, const float* rmax, c
     float* rp = work;
     float* cp = work + (size_t)V * nct * R;
     const dim3 grid((unsigned)((size_t)V * nrt * nct));
-    if (C % 4 == 0)
-      hipLaunchKernelGGL((mm_bwd_sums2d_kernel<true>), grid, dim3(256), 0, s, c, g, rmax, cmax, R, C, nrt, nct, rp, cp, eps);
-    else
-      hipLaunchKernelGGL((mm_bwd_sums2d_kernel<false>), grid, dim3(256), 0, s, c, g, rmax, cmax, R, C, nrt, nct, rp, cp, eps);
+    dispatch_bool(C % 4 == 0, [&](auto vc) {   // 16-byte rows: vector loads
+      hipLaunchKernelGGL((mm_bwd_sums2d_kernel<decltype(vc)::value>), grid, dim3(256), 0, s, c, g, rmax, cmax, R, C, nrt,
+                         nct, rp, cp, eps);
+    });
     hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)cdiv(V * R, 256)), dim3(256), 0, s, rp, rsum, V, R, nct);
     hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)cdiv(V * C, 256)), dim3(256), 0, s, cp, csum, V, C, nrt);
   } else {
@@ -865,14 +859,21 @@ extern "C" int ncnet_maxpool4d(const void* x, int x_is_bf16, float* y, uint8_t* 
   if (ks > 4 || ks < 1) return -1;
   long long total = (long long)V * (I / ks) * (J / ks) * (K / ks) * (L / ks);
   dim3 grid((unsigned)((total + 255) / 256));
-  if (x_is_bf16) hipLaunchKernelGGL((maxpool4d_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)x, y, code, V, I, J, K, L, ks);
-  else hipLaunchKernelGGL((maxpool4d_kernel<float>), grid, dim3(256), 0, s, (const float*)x, y, code, V, I, J, K, L, ks);
+  auto launch = [&](auto* xt) {
+    using T = std::remove_pointer_t<decltype(xt)>;
+    hipLaunchKernelGGL((maxpool4d_kernel<T>), grid, dim3(256), 0, s, (const T*)x, y, code, V, I, J, K, L, ks);
+  };
+  if (x_is_bf16) launch((bf16*)nullptr); else launch((float*)nullptr);
   return (int)hipGetLastError();
 }
 extern "C" int ncnet_transpose(const void* x, void* y, int elem_bytes, int V, int R, int C, hipStream_t s) {
   dim3 grid(tiles64(V, R, C));
-  if (elem_bytes == 2) hipLaunchKernelGGL((transpose_kernel<bf16>), grid, dim3(256), 0, s, (const bf16*)x, (bf16*)y, R, C);
-  else if (elem_bytes == 4) hipLaunchKernelGGL((transpose_kernel<float>), grid, dim3(256), 0, s, (const float*)x, (float*)y, R, C);
+  auto launch = [&](auto* xt) {
+    using T = std::remove_pointer_t<decltype(xt)>;
+    hipLaunchKernelGGL((transpose_kernel<T>), grid, dim3(256), 0, s, (const T*)x, (T*)y, R, C);
+  };
+  if (elem_bytes == 2) launch((bf16*)nullptr);
+  else if (elem_bytes == 4) launch((float*)nullptr);
   else return -1;
   return (int)hipGetLastError();
 }

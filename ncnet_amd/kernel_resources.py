@@ -7,7 +7,7 @@ VGPRs, AGPRs, SGPRs, scratch bytes per lane, spilled VGPRs/SGPRs, occupancy
 fail the CPU suite when a hot kernel starts spilling (the round-2 regression:
 conv16v3 fwd/dgrad picked up scratch from a release-mode codegen change).
 
-    python -m ncnet_amd.kernel_resources [--md out.md] [file.hip ...]
+    python -m ncnet_amd.kernel_resources [--full] [--md out.md] [file.hip ...]
 """
 from __future__ import annotations
 
@@ -44,6 +44,44 @@ def demangle(name: str) -> str:
         vals = [("true" if v == "1" else "false") if t == "b" else v for t, v in args]
         return f"{ident}<{', '.join(vals)}>"
     return ident
+
+
+def full_name(mangled: str) -> str:
+    """Kernel name with every template argument, type arguments included
+    (``ijpack_kernel<bf16, 5, false, true>``), for names inside namespace
+    ``ncnet`` (and nested ones) or at global scope.  The same decoding applies
+    to the mangled names a profiler reports (rocprofv3 --mangled-kernels), so
+    resource tables and launch tables can be compared by name."""
+    mangled = re.sub(r"\.kd$", "", mangled)
+    m = re.match(r"_ZN5ncnet", mangled)
+    if not m:
+        m2 = re.match(r"_Z(\d+)", mangled)
+        return mangled[m2.end():m2.end() + int(m2.group(1))] if m2 else mangled
+    pos, ident = m.end(), ""
+    while True:                                   # nested namespaces, then the identifier
+        m2 = re.match(r"\d+", mangled[pos:])
+        if not m2:
+            break
+        n = int(m2.group(0))
+        ident = mangled[pos + m2.end():pos + m2.end() + n]
+        pos += m2.end() + n
+    rest = mangled[pos:]
+    if not rest.startswith("I"):
+        return ident
+    rest, args = rest[1:], []
+    while rest and not rest.startswith("E"):
+        if rest.startswith("DF16b"):
+            args.append("bf16"); rest = rest[5:]
+        elif rest.startswith("f"):
+            args.append("float"); rest = rest[1:]
+        else:
+            m3 = re.match(r"L(i|b|N\w*?E)(n?\d+)E", rest)
+            if not m3:
+                args.append("?" + rest[:12]); break
+            v = m3.group(2).replace("n", "-")
+            args.append(("true" if v == "1" else "false") if m3.group(1) == "b" else v)
+            rest = rest[m3.end():]
+    return f"{ident}<{', '.join(args)}>"
 
 
 def _cached_remarks(src: Path) -> str | None:
@@ -114,13 +152,24 @@ def to_markdown(recs) -> str:
     return "\n".join(lines) + "\n"
 
 
+def to_markdown_full(recs) -> str:
+    """Every record by full name (sorted), with the mangled name and the static LDS size."""
+    lines = ["| kernel | mangled | LDS B/block | VGPR | AGPR | SGPR | scratch B/lane | waves/SIMD |",
+             "|---|---|---:|---:|---:|---:|---:|---:|"]
+    for name, r in sorted((full_name(r["mangled"]), r) for r in recs):
+        lines.append(f"| `{name}` | `{r['mangled']}` | {r.get('lds')} | {r.get('vgpr')} | {r.get('agpr')} "
+                     f"| {r.get('sgpr')} | {r.get('scratch')} | {r.get('occupancy')} |")
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("srcs", nargs="*")
     ap.add_argument("--md", default=None, help="write a markdown table here")
+    ap.add_argument("--full", action="store_true", help="full names, mangled names and LDS, sorted by name")
     a = ap.parse_args(argv)
     recs = analyse_all(a.srcs)
-    md = to_markdown(recs)
+    md = to_markdown_full(recs) if a.full else to_markdown(recs)
     if a.md:
         Path(a.md).write_text(md)
     print(md)

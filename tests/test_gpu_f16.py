@@ -46,6 +46,50 @@ def test_corr_gemm_f16(v2, tune):
     assert rl2(o16, want) < 1e-3
 
 
+@pytest.mark.parametrize("kind,v2,ns", [("f16", 1, 4), ("bf16", 1, 3), ("bf16", 1, 4), ("bf16", 0, 3),
+                                        ("fp8", 0, 3), ("fp8", 1, 3)])
+def test_corr_gemm_16bit_out(kind, v2, ns, tune):
+    """corr_gemm with a 16-bit C for every operand type and kernel that no other test
+    launches that way: the v2 ring at 3 / 4 stages (f16, bf16), the v1 kernel (bf16,
+    fp8) and the fp8 v2 ring, vs an fp64 GEMM of the same operand values.  Bounds:
+    fp32 C 1e-5 and f16 C 1e-3 as test_corr_gemm_f16; bf16 C 4e-3 (2^-9 rounding
+    per element, so at most 2^-8 in the l2 ratio)."""
+    tune("corr_v2", v2)
+    tune("corr_ns", ns)
+    torch.manual_seed(1)
+    dt = {"f16": torch.float16, "bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}[kind]
+    K = 1024 if kind == "fp8" else 256
+    a = (torch.randn(2, 300, K, device=DEV) * 0.25).to(dt)
+    b = (torch.randn(2, 290, K, device=DEV) * 0.25).to(dt)
+    scale = 0.5 if kind == "fp8" else 1.0
+    m = torch.arange(2, device=DEV, dtype=torch.int32)
+    want = scale * torch.bmm(a.float().double(), b.float().double().transpose(1, 2))
+    c16 = torch.float16 if kind == "f16" else torch.bfloat16
+    o16 = torch.full((2, 300, 290), float("nan"), device=DEV, dtype=c16)
+    _ext.ext().corr_gemm(a, b, o16, m, m, scale)
+    assert rl2(o16, want) < (1e-3 if kind == "f16" else 4e-3)
+    if kind == "f16":
+        out = torch.full((2, 300, 290), float("nan"), device=DEV)
+        _ext.ext().corr_gemm(a, b, out, m, m, 1.0)
+        assert rl2(out, want) < 1e-5
+
+
+@pytest.mark.parametrize("ns", [3, 4])
+def test_corr_pool2_f16_v2_ring(ns, tune):
+    """The fused-pool f16 correlation on the v2 ring (corr_v2 forced, 3 / 4 stages) on the
+    oracle and bound of test_corr_pool2_f16_matches_unfused."""
+    from ncnet_amd.ops.correlation import correlation_pool2
+    tune("corr_v2", 1)
+    tune("corr_ns", ns)
+    torch.manual_seed(2)
+    fa = torch.nn.functional.normalize(torch.randn(1, 12 * 16, 256, device=DEV), dim=2).half()
+    fb = torch.nn.functional.normalize(torch.randn(1, 10 * 14, 256, device=DEV), dim=2).half()
+    val, _ = correlation_pool2(fa, fb, 12, 16, 10, 14)
+    full = torch.bmm(fa.float(), fb.float().transpose(1, 2)).view(1, 1, 12, 16, 10, 14)
+    want, _ = ref.maxpool4d(full, 2)
+    assert rl2(val, want) < 1e-5
+
+
 def test_corr_pool2_f16_matches_unfused():
     from ncnet_amd.ops.correlation import correlation_pool2
     torch.manual_seed(2)
@@ -92,16 +136,53 @@ def test_fused_nc_f16_vs_fp64():
 @pytest.mark.parametrize("k,stride,cin,cout,res", [(1, 1, 256, 128, False), (3, 1, 128, 128, True),
                                                     (3, 2, 64, 128, False), (1, 1, 512, 1024, True)])
 def test_conv2d_nhwc_f16(k, stride, cin, cout, res):
+    _conv2d_nhwc_f16_vs_fp32(k, stride, cin, cout, res, (2, 20, 24))
+
+
+@pytest.mark.parametrize("variant,k,cout,shape", [(1, 1, 128, (2, 184, 184)), (1, 1, 64, (2, 184, 184)),
+                                                  (1, 1, 64, (2, 20, 24)), (0, 3, 128, (4, 160, 208))])
+def test_conv2d_nhwc_f16_tiles(variant, k, cout, shape, tune):
+    """The f16 tiles no other test launches: the register-staged kernel (conv2d_variant
+    1) at 128 x 128 and 128 x 64 (>= 512 workgroups of 128 rows) and 64 x 64, and the
+    256 x 128 DMA ring (auto from 384 tiles of 256 rows); oracle and bound of
+    test_conv2d_nhwc_f16."""
+    tune("conv2d_variant", variant)
+    _conv2d_nhwc_f16_vs_fp32(k, 1, 64, cout, True, shape)
+
+
+@pytest.mark.parametrize("cfg", [(10, 4, 15, 20), (20, 4, 15, 20), (8, 3, 19, 17), (24, 4, 15, 20)])
+def test_nc_fused_k3_f16_tiles(cfg):
+    """nc_fused_k3 on IEEE-half operands at the compile-time tiles (15 x 20 with R 10 and, on
+    16 waves, R 20; 19 x 17 with R 8) and the generic 16-wave kernel (R 24), cfg = (R, IR,
+    TK, TL), vs fp64 on the same f16 input; the bound of test_fused_nc_f16_vs_fp64."""
+    import importlib
+    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
+    torch.manual_seed(4)
+    V, I, J, K, L = 1, 6, 26, 17, 22
+    w1 = ref.conv4d_weight_from_std(torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2)
+    w2 = ref.conv4d_weight_from_std(torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.05)
+    b1, b2 = torch.rand(16, device=DEV) * 0.05, torch.rand(1, device=DEV) * 0.05
+    x = torch.rand(V, I, J, K, L, device=DEV).half()
+    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
+    R, IR, tk, tl = cfg
+    _ext.ext().nc_fused_k3(x, *nc._fused_weights([w1, w2], [b1, b2], torch.float16), y, R, IR, tk, tl)
+    want = ref.neigh_consensus(x.double().unsqueeze(1), [w1.double(), w2.double()], [b1.double(), b2.double()], False)
+    assert torch.isfinite(y).all()
+    assert rl2(y, want.squeeze(1)) < 3e-3
+
+
+def _conv2d_nhwc_f16_vs_fp32(k, stride, cin, cout, res, shape):
     torch.manual_seed(5)
     cl = torch.channels_last
-    x = torch.randn(2, cin, 20, 24, device=DEV).half().contiguous(memory_format=cl)
+    n, h0, w0 = shape
+    x = torch.randn(n, cin, h0, w0, device=DEV).half().contiguous(memory_format=cl)
     w = (torch.randn(cout, cin, k, k, device=DEV) / (cin * k * k) ** 0.5).half().contiguous(memory_format=cl)
     b = torch.randn(cout, device=DEV) * 0.1
     pad = k // 2
-    ho = (20 + 2 * pad - k) // stride + 1
-    wo = (24 + 2 * pad - k) // stride + 1
-    r = torch.randn(2, cout, ho, wo, device=DEV).half().contiguous(memory_format=cl) if res else None
-    y = torch.empty(2, cout, ho, wo, device=DEV, dtype=torch.float16, memory_format=cl)
+    ho = (h0 + 2 * pad - k) // stride + 1
+    wo = (w0 + 2 * pad - k) // stride + 1
+    r = torch.randn(n, cout, ho, wo, device=DEV).half().contiguous(memory_format=cl) if res else None
+    y = torch.empty(n, cout, ho, wo, device=DEV, dtype=torch.float16, memory_format=cl)
     _ext.ext().conv2d_nhwc(x, w, b, r, y, stride, pad, 1)
     want = F.conv2d(x.float(), w.float(), b, stride, pad)
     if res:

@@ -212,7 +212,11 @@ def test_cout1_taps_fwd(shape, cin, relu):
 
 @pytest.mark.parametrize("ks,shape,nx,ng", [(5, (2, 25, 25, 25, 25), 1, 2), (5, (2, 25, 25, 25, 25), 2, 1),
                                             (3, (2, 7, 9, 11, 13), 1, 1), (7, (1, 9, 8, 25, 25), 1, 2),
-                                            (1, (2, 5, 6, 20, 25), 2, 1)])
+                                            (1, (2, 5, 6, 20, 25), 2, 1),
+                                            # instantiations no other test launches, 7 x 9 planes (63 voxels,
+                                            # no multiple of 16): wgrad16p<3, 2>, <1, 2>, <7, 1>
+                                            (3, (1, 5, 7, 7, 9), 1, 2), (1, (1, 5, 7, 7, 9), 1, 2),
+                                            (7, (1, 5, 7, 7, 9), 1, 1)])
 def test_wgrad16p(ks, shape, nx, ng):
     """Double-buffered plane-only weight gradient (both ij groups per launch)
     vs the fp64 plane-conv definition: dW[tap][ci][co] = sum X[vox + tap] G[vox]."""
@@ -313,6 +317,17 @@ def test_neigh_consensus_autograd(ks, ch, shape):
 
 @pytest.mark.parametrize("shape", [(3, 1, 25, 25, 25, 25), (2, 1, 7, 9, 11, 5), (2, 1, 8, 10, 16, 20)])
 def test_mutual_matching(shape):
+    _mutual_matching_vs_fp64(shape)
+
+
+def test_mutual_matching_two_pass_backward(runtime):
+    """mm_bwd with one_pass = False (config stats2d off): the separate
+    mm_bwd_rowsum / mm_bwd_colsum kernels, on the same oracle and bounds."""
+    runtime(stats2d=False)
+    _mutual_matching_vs_fp64((2, 1, 7, 9, 11, 5))
+
+
+def _mutual_matching_vs_fp64(shape):
     from ncnet_amd.ops.mutual import mutual_matching
     torch.manual_seed(5)
     c = torch.rand(shape, device=DEV, requires_grad=True)
@@ -338,6 +353,37 @@ def test_l2norm_and_correlation():
     c = correlation(p, p, amap, bmap)
     cr = torch.bmm(p.double()[amap.long()], p.double()[bmap.long()].transpose(1, 2))
     assert relerr(c, cr) < 1e-3
+
+
+def test_l2norm_rows_bwd_kernel():
+    """l2norm_rows_bwd (the gradient of x / sqrt(sum x^2 + 1e-6) per row, fp32) vs
+    fp64 autograd; C = 40 is no multiple of the 64 lanes, 7 rows leave the last
+    block of 4 partial.  fp32 in and out: 1e-5 covers the ~100 fp32 operations per element."""
+    C = _ext.ext()
+    torch.manual_seed(8)
+    x = torch.randn(7, 40, device=DEV)
+    g = torch.randn(7, 40, device=DEV)
+    y = torch.empty(7, 40, device=DEV, dtype=torch.bfloat16)
+    inv = torch.empty(7, device=DEV)
+    C.l2norm_rows(x, y, inv, 0.0, None)
+    gx = torch.full((7, 40), float("nan"), device=DEV)
+    C.l2norm_rows_bwd(x, g, inv, gx)
+    xr = x.double().requires_grad_(True)
+    ((xr / torch.sqrt((xr * xr).sum(1, keepdim=True) + 1e-6)) * g.double()).sum().backward()
+    assert relerr(gx, xr.grad) < 1e-5
+
+
+def test_maxpool4d_bf16_input():
+    """maxpool4d_kernel<bf16> (the suite pools fp32 volumes): values and offsets equal
+    the reference pool of the same bf16 values exactly."""
+    from ncnet_amd.ops.correlation import maxpool4d
+    torch.manual_seed(9)
+    v = torch.rand(2, 1, 6, 8, 4, 10, device=DEV).to(torch.bfloat16)
+    val, off = maxpool4d(v, 2)
+    vr, offr = ref.maxpool4d(v.float().cpu(), 2)
+    assert torch.equal(val.cpu(), vr)
+    for a, b in zip(off, offr):
+        assert torch.equal(a.cpu().long(), b.long())
 
 
 def test_correlation_odd_sizes_and_grad():
@@ -424,6 +470,27 @@ def test_correlation_v2_large_grids():
         assert (a.long() == b.long()).float().mean() > 0.999
 
 
+def test_correlation_v2_four_stage_ring(tune):
+    """corr_gemm_v2 with the 4-stage ring (tuning switch corr_ns at 4; 3 everywhere
+    else), plain store and fused pool, forced onto a small grid (corr_v2 = 1) with a
+    full and a ragged tile along M and N; the oracles and bounds of
+    test_correlation_v2_large_grids."""
+    from ncnet_amd.ops.correlation import correlation, correlation_pool2, maxpool4d
+    tune("corr_v2", 1)
+    tune("corr_ns", 4)
+    torch.manual_seed(10)
+    hA, wA, hB, wB = 18, 20, 10, 14
+    fa = torch.nn.functional.normalize(torch.randn(2, hA * wA, 1024, device=DEV), dim=-1).to(torch.bfloat16).float()
+    fb = torch.nn.functional.normalize(torch.randn(2, hB * wB, 1024, device=DEV), dim=-1).to(torch.bfloat16).float()
+    c = correlation(fa, fb)
+    assert relerr(c, torch.bmm(fa.double(), fb.double().transpose(1, 2))) < 1e-5
+    pv, po = correlation_pool2(fa, fb, hA, wA, hB, wB)
+    rv, ro = maxpool4d(c.view(2, 1, hA, wA, hB, wB), 2)
+    assert relerr(pv, rv) < 1e-6
+    for a, b in zip(po, ro):
+        assert (a.long() == b.long()).float().mean() > 0.999
+
+
 @pytest.mark.parametrize("shape,ng", [((2, 6, 5, 25, 25), 7), ((3, 25, 25, 25, 25), 102), ((1, 4, 7, 25, 25), 1),
                                       ((2, 9, 3, 25, 25), 40)])
 def test_wgrad16v4_matches_v3(shape, ng, monkeypatch, tune):
@@ -450,7 +517,9 @@ def test_wgrad16v4_matches_v3(shape, ng, monkeypatch, tune):
 
 @pytest.mark.parametrize("variant", [2, 3])
 @pytest.mark.parametrize("ks,shape", [(5, (2, 6, 5, 25, 25)), (5, (1, 5, 4, 30, 27)), (3, (1, 4, 5, 9, 33)),
-                                      (5, (1, 2, 3, 7, 6)), (7, (1, 3, 4, 25, 25)), (1, (1, 3, 4, 25, 26))])
+                                      (5, (1, 2, 3, 7, 6)), (7, (1, 3, 4, 25, 25)), (1, (1, 3, 4, 25, 26)),
+                                      # 13 x 14 = 182 voxels: one tile of VT = 192, the 3-chunk wgrad16v3<3, 3>
+                                      (3, (1, 2, 3, 13, 14))])
 def test_wgrad16_kernel(variant, ks, shape):
     """Weight / bias gradient of a 16->16 Conv4d straight from the wgrad16
     kernels (v3 sliding ring for KS 3/5 when the row fits, v2 per plane
@@ -509,7 +578,10 @@ def test_wgrad16v3_priority_flag(flags, monkeypatch, tune):
                                                 (3, -1, (2, 3, 3, 7, 5), torch.bfloat16),
                                                 (5, 1, (1, 3, 4, 40, 30), torch.bfloat16),
                                                 (7, 1, (1, 8, 9, 6, 7), torch.bfloat16),
-                                                (1, -1, (1, 3, 4, 6, 7), torch.float32)])
+                                                (1, -1, (1, 3, 4, 6, 7), torch.float32),
+                                                # ijpack<float, 3> and <float, 7>
+                                                (3, 1, (1, 2, 3, 7, 9), torch.float32),
+                                                (7, -1, (1, 4, 5, 7, 9), torch.float32)])
 def test_ijpack_kernel(ks, sgn, shape, dtype):
     """ijpack vs the torch emulation of the ij encoding:
     S[g][v,i,j,k,l,c] = X[v, i+sgn*(di-P), j+sgn*(dj-P), k, l], q = 16g + c."""
@@ -521,6 +593,80 @@ def test_ijpack_kernel(ks, sgn, shape, dtype):
     _ext.ext().ijpack(x, s, ks, sgn)
     want = _ijpack(x.float().cpu(), ks, sgn).permute(0, 1, 3, 4, 5, 6, 2).to(torch.bfloat16)
     assert torch.equal(s.cpu(), want)
+
+
+@pytest.mark.parametrize("ks,dtype", [(1, torch.bfloat16), (5, torch.bfloat16), (7, torch.bfloat16),
+                                      (1, torch.float32), (3, torch.float32), (5, torch.float32),
+                                      (7, torch.float32)])
+def test_ijpack_kernel_fp8_out(ks, dtype):
+    """ijpack with the OCP e4m3 output of the fp8 inference path, the (input type,
+    KS) instantiations no other test launches, vs the same torch emulation rounded
+    to e4m3 (round to nearest even on both sides; |x| stays far below 448)."""
+    from tests.test_kernel_emulation import _ijpack
+    torch.manual_seed(13)
+    shape = (1, 4, 5, 7, 9)          # I, J > KS / 2: every (di, dj) shift keeps part of the volume
+    x = torch.randn(shape, device=DEV).to(dtype)
+    G = (ks * ks + 15) // 16
+    s = torch.zeros((G,) + shape + (16,), device=DEV).to(torch.float8_e4m3fn)
+    _ext.ext().ijpack(x, s, ks, 1)
+    want = _ijpack(x.float().cpu(), ks, 1).permute(0, 1, 3, 4, 5, 6, 2).to(torch.float8_e4m3fn)
+    assert torch.equal(s.float().cpu(), want.float())
+
+
+@pytest.mark.parametrize("ks", [1, 7])
+@pytest.mark.parametrize("relu,sgn", [(1, 1), (0, -1)])
+def test_ijsum_kernel(ks, relu, sgn):
+    """ijsum<1> and <7> (the NC stacks of the suite only sum KS 3 / 5) vs the fp64 emulation."""
+    from tests import emu_ext
+    torch.manual_seed(17)
+    shape = (1, 4, 5, 7, 9)
+    z = torch.randn((ks * ks,) + shape, device=DEV)
+    b = torch.randn(1, device=DEV)
+    y = torch.full(shape, float("nan"), device=DEV)
+    _ext.ext().ijsum(z, b, y, ks, relu, sgn)
+    want = torch.empty(shape, dtype=torch.float64)
+    emu_ext.ijsum(z.cpu(), b.cpu(), want, ks, relu, sgn)
+    assert relerr(y, want) < 1e-6          # fp32 sums of <= 49 terms
+
+
+@pytest.mark.parametrize("ks,epi,grp", [(1, 0, 0), (1, 0, 2), (1, 2, 0), (1, 2, 2), (1, 4, 2),
+                                        (7, 0, 0), (7, 0, 2), (7, 2, 0), (7, 2, 2),
+                                        (3, 0, 0), (3, 0, 2), (5, 0, 0), (5, 0, 2)])
+def test_conv16_fwd_v2_epilogues(ks, epi, grp):
+    """The conv16v2 (KS, epilogue, group-plane) instantiations no other test launches:
+    no epilogue (0) at every KS, the ReLU mask (2) and planar fp32 (4) at KS 1 / 7, each
+    with all (di, dj) planes (grp 0) and in group-plane mode (grp input groups, several
+    output j-tiles per workgroup), on 7 x 9 planes (63 voxels, no multiple of 16) vs
+    fp64 math on the same bf16 operands; the bounds of test_conv16_fwd (bf16 output)
+    and test_conv16_fp8_kernel (planar fp32)."""
+    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
+    torch.manual_seed(4)
+    V, I, J, K, L = 1, 2, 6, 7, 9
+    if grp:
+        x = torch.rand(grp, V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
+        w = (torch.randn(grp, 16, 16, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
+        wp = pack_w16_planes(w)
+        xx = x.double().permute(0, 1, 2, 3, 6, 4, 5).reshape(grp, V * I * J, 16, K, L)
+        yr = sum(torch.nn.functional.conv2d(xx[g], w[g].double(), padding=ks // 2) for g in range(grp))
+        yr = yr.reshape(V, I, J, 16, K, L).permute(0, 3, 1, 2, 4, 5)          # [V, 16, I, J, K, L]
+    else:
+        xs = torch.rand(V, 16, I, J, K, L, device=DEV)
+        x = xs.permute(0, 2, 3, 4, 5, 1).contiguous().to(torch.bfloat16)
+        w = torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05
+        wp = pack_w16(w)
+        yr = ref.conv4d(bf(xs), ref.conv4d_weight_from_std(bf(w)), None)
+    m = None
+    if epi == 2:
+        m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
+        yr = yr * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
+    if epi == 4:
+        y = torch.full((16, V, I, J, K, L), float("nan"), device=DEV)
+        _ext.ext().conv16_fwd(x, wp.to(torch.bfloat16), None, None, y, ks, 4)
+        assert relerr(y.permute(1, 0, 2, 3, 4, 5), yr) < 1e-4
+    else:
+        y = torch.full((V, I, J, K, L, 16), float("nan"), device=DEV).to(torch.bfloat16)
+        _ext.ext().conv16_fwd(x, wp.to(torch.bfloat16), None, m, y, ks, epi)
+        assert relerr(y.permute(0, 5, 1, 2, 3, 4), yr) < 1e-2
 
 
 def test_bias_act_kernel():
@@ -535,6 +681,22 @@ def test_bias_act_kernel():
     refz = z.float() + b.repeat(2)
     C.bias_act_(z, b.repeat(2).contiguous(), 0)
     assert relerr(z, refz) < 1e-2
+
+
+def test_bias_act_kernel_f16():
+    """bias_act_kernel<*, true>: IEEE-half tensors (the fp16 trunk), channels-last with
+    ReLU and a [rows, C] matrix without; f16 rounding is 2^-11, so 1e-3."""
+    C = _ext.ext()
+    torch.manual_seed(5)
+    y = torch.randn(2, 64, 9, 7, device=DEV).half().contiguous(memory_format=torch.channels_last)
+    b = torch.randn(64, device=DEV)
+    ref_ = torch.relu(y.float() + b.view(1, -1, 1, 1))
+    C.bias_act_(y, b, 1)
+    assert relerr(y, ref_) < 1e-3
+    z = torch.randn(33, 128, device=DEV).half()
+    refz = z.float() + b.repeat(2)
+    C.bias_act_(z, b.repeat(2).contiguous(), 0)
+    assert relerr(z, refz) < 1e-3
 
 
 def test_frozen_trunk_plan_gpu():
@@ -619,7 +781,9 @@ def test_immatchnet_fp8_correlation_path():
     assert rel_l2(c8, c16) < 0.1
 
 
-@pytest.mark.parametrize("ks,shape", [(5, (2, 25, 25, 25, 25)), (3, (1, 7, 9, 30, 27))])
+@pytest.mark.parametrize("ks,shape", [(5, (2, 25, 25, 25, 25)), (3, (1, 7, 9, 30, 27)),
+                                      # conv16f8<7, *> and <1, *>: 7 x 9 planes (63 voxels, no multiple of 16)
+                                      (7, (1, 2, 3, 7, 9)), (1, (1, 2, 3, 7, 9))])
 def test_conv16_fp8_kernel(ks, shape):
     """fp8 (OCP e4m3) inference conv16 vs fp64 math on the same fp8 values:
     bias+ReLU -> fp8 output and planar fp32 output, plain and group-plane mode."""
@@ -738,6 +902,18 @@ def test_nc_forward_deterministic_and_fully_written():
 def test_conv2d_nhwc_kernel(cin, cout, k, stride, pad, res, relu, shape):
     """NHWC implicit-GEMM conv (+bias, +residual, ReLU) vs F.conv2d in fp64 on bf16 inputs
     (both the 64- and 128-row tile variants)."""
+    _conv2d_nhwc_vs_fp64(cin, cout, k, stride, pad, res, relu, shape)
+
+
+@pytest.mark.parametrize("cout,shape", [(128, (2, 19, 23)), (64, (2, 19, 23)), (128, (4, 129, 127)), (64, (4, 129, 127))])
+def test_conv2d_nhwc_dma_ring_small_tiles(cout, shape, tune):
+    """conv2d_nhwc_v2<64 / 128, 64 / 128, 4, 4>: the DMA ring forced at the small tiles
+    (conv2d_variant 2; BN by Cout, 128-row tiles from 512 workgroups) on the same oracle and bound."""
+    tune("conv2d_variant", 2)
+    _conv2d_nhwc_vs_fp64(64, cout, 3, 1, 1, True, True, shape)
+
+
+def _conv2d_nhwc_vs_fp64(cin, cout, k, stride, pad, res, relu, shape):
     C = _ext.ext()
     torch.manual_seed(17)
     cl = torch.channels_last
@@ -751,7 +927,7 @@ def test_conv2d_nhwc_kernel(cin, cout, k, stride, pad, res, relu, shape):
         yr = yr + r.double()
     if relu:
         yr = torch.relu(yr)
-    y = torch.empty(yr.shape, dtype=torch.bfloat16, device=DEV).contiguous(memory_format=cl)
+    y = torch.full(yr.shape, float("nan"), dtype=torch.bfloat16, device=DEV).contiguous(memory_format=cl)
     C.conv2d_nhwc(x, w, b, r, y, stride, pad, 1 if relu else 0)
     assert relerr(y, yr) < 1e-2
 
@@ -791,7 +967,12 @@ def test_conv2d_nhwc_256x256_tile(cin, cout, k, stride, pad, res, relu, shape, t
     (256, 256, 3, 2, 1, False, True, (2, 50, 50), torch.bfloat16),     # stride-2 3x3
     (512, 1024, 1, 2, 0, False, False, (2, 50, 50), torch.bfloat16),   # stride-2 downsample
     (128, 128, 3, 1, 1, True, True, (3, 23, 19), torch.bfloat16),      # Cout 128: the 128-column tile
-    (256, 256, 3, 1, 1, True, True, (3, 25, 25), torch.float16)])     # IEEE half operands
+    (256, 256, 3, 1, 1, True, True, (3, 25, 25), torch.float16),      # IEEE half operands
+    (128, 64, 3, 1, 1, False, True, (1, 20, 20), torch.float16)] +     # TM 3 at the 64-column tile, f16
+    # tile rows TM 4 / 5 / 6 (c3_pick_tm on the 256 CUs of an MI355X: M = 256 x 16 TM pixels is one round
+    # of TM-row tiles and two rounds of the next smaller ones) at the 64 / 128 / 256-column tiles
+    [(128, cout, 3, 1, 1, False, True, (1, 128, wd), dt) for wd in (128, 160, 192) for cout in (64, 128, 256)
+     for dt in (torch.bfloat16, torch.float16)])
 def test_conv2d_nhwc_v3(cin, cout, k, stride, pad, res, relu, shape, dt, tune):
     """conv2d_nhwc_v3 (one round of chip-sized workgroups: 16 TM x 64 TN tiles,
     8 waves as 2 K-groups x 4 N-groups, LDS-DMA ring, K-group sum in the
@@ -959,7 +1140,10 @@ def test_debug_build_selftest(capfd):
         assert r == 1 and "NCNET_CHECK" not in text
 
 
-@pytest.mark.parametrize("cfg", [None, (3, 4, 6, 7), (2, 3, 16, 20), (5, 2, 9, 11)])
+@pytest.mark.parametrize("cfg", [None, (3, 4, 6, 7), (2, 3, 16, 20), (5, 2, 9, 11),
+                                 # compile-time tiles no other test launches: <19, 17, R 8> and the
+                                 # 16-wave <15, 20, R 20>
+                                 (8, 3, 19, 17), (20, 4, 15, 20)])
 def test_nc_fused_k3_vs_quantized_oracle(cfg):
     """The fused InLoc NeighConsensus kernel (csrc/nc_fused.hip: 1 -> 16 -> 1,
     k = 3, hidden layer in LDS) against the fp64 oracle with bf16 rounding of
@@ -987,13 +1171,29 @@ def test_nc_fused_k3_vs_quantized_oracle(cfg):
 
 
 @pytest.mark.parametrize("shape", [(1, 7500, 7500), (3, 625, 400), (2, 130, 1852), (1, 64, 256), (4, 625, 625),
-                                   (2, 77, 1850), (1, 3, 5)])
+                                   (2, 77, 1850), (1, 3, 5),
+                                   # R >= 1024 with C % 4 != 0: the scalar-load tile kernel at two 64-row
+                                   # sub-tiles per block (stats2d_tile<*, false, 2>), last block partial
+                                   (1, 1030, 7)])
 @pytest.mark.parametrize("sum_kind", [0, 1, 2])
 def test_stats2d_matches_row_and_col_kernels(shape, sum_kind):
     """One-pass row + column statistics (csrc/volume.hip stats2d; 16-byte
     loads, or scalar loads when C % 4 != 0) equal the separate stats_rows /
     stats_cols kernels: max and first argmax exactly (values drawn from a small
     set: many ties), the sums to fp32 rounding."""
+    _stats2d_vs_row_and_col_kernels(shape, sum_kind)
+
+
+@pytest.mark.parametrize("shape", [(1, 1030, 8), (1, 1030, 7)])
+@pytest.mark.parametrize("sum_kind", [0, 1, 2])
+def test_stats2d_four_subtiles(shape, sum_kind, tune):
+    """stats2d_tile<*, *, 4> (tuning switch s2d_rt at 4, R >= 1024; 16-byte and scalar
+    loads, last block partial) against the same separate kernels."""
+    tune("s2d_rt", 4)
+    _stats2d_vs_row_and_col_kernels(shape, sum_kind)
+
+
+def _stats2d_vs_row_and_col_kernels(shape, sum_kind):
     V, R, C = shape
     torch.manual_seed(31)
     x = (torch.randint(0, 50, shape, device=DEV).float() / 7.0 - 3.0).contiguous()
@@ -1187,6 +1387,20 @@ def test_conv1x16_vs_oracle(ks, shape, epi):
     gathered by ds_read_b64_tr_b16 from 4 element-shifted LDS copies of each
     plane) vs the fp64 oracle: bias + ReLU forward, and the ReLU-mask epilogue
     of the last layer's data gradient."""
+    _conv1x16_vs_oracle(ks, shape, epi)
+
+
+@pytest.mark.parametrize("pd", [1, 3])
+@pytest.mark.parametrize("epi", [1, 2])
+def test_conv1x16_lookahead_variants(pd, epi, tune):
+    """The transposed-read lookahead variants conv1x16<5, 5, epi, 25, 25, PD = 1 / 3>
+    (tuning switch c1x_pd; the default 2 runs everywhere else) on the same oracle and
+    bound; J = 6 leaves the second block of 5 output j-planes partial."""
+    tune("c1x_pd", pd)
+    _conv1x16_vs_oracle(5, (1, 2, 6, 25, 25), epi)
+
+
+def _conv1x16_vs_oracle(ks, shape, epi):
     from ncnet_amd.ops.packing import pack_w1x
     torch.manual_seed(3)
     V, I, J, K, L = shape
@@ -1414,4 +1628,19 @@ def test_maxpool_bias_act_matches_separate_passes(dtype, hw):
     ho, wo = want.shape[2:]
     y = torch.empty((3, 64, ho, wo), dtype=dtype, device=DEV, memory_format=torch.channels_last)
     _ext.ext().maxpool_bias_act(x, b, y, 3, 2, 1, 1)
+    assert torch.equal(y, want)
+
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_maxpool_bias_act_without_relu(dtype):
+    """maxpool_bias_act_kernel<false, *>: bias + max-pool without the ReLU equals the
+    rounded bias add followed by max_pool2d bit for bit (rounding is monotonic)."""
+    torch.manual_seed(41)
+    x = torch.randn(2, 64, 37, 61, device=DEV).to(dtype).contiguous(memory_format=torch.channels_last)
+    b = torch.randn(64, device=DEV)
+    want = torch.nn.functional.max_pool2d((x.float() + b.view(1, -1, 1, 1)).to(dtype), 3, 2, 1)
+    ho, wo = want.shape[2:]
+    y = torch.empty((2, 64, ho, wo), dtype=dtype, device=DEV, memory_format=torch.channels_last)
+    _ext.ext().maxpool_bias_act(x, b, y, 3, 2, 1, 0)
     assert torch.equal(y, want)

@@ -82,12 +82,25 @@ def _split(t):
 def test_conv16_x3_kernel_vs_emulator(grp, plane, epi):
     """One conv16_fwd_x3 launch (group-plane or full (di, dj) sum; bias+ReLU or
     ReLU-mask epilogue) against the fp64 emulator: hi + lo to ~1e-5."""
+    _conv16_x3_vs_emulator(grp, plane, epi, 5, (2, 6, 5))
+
+
+@pytest.mark.parametrize("ks,plane", [(5, 15), (3, 15), (3, 20), (3, 25), (3, 30)])
+@pytest.mark.parametrize("epi", [1, 2])
+def test_conv16_x3_v4_planes_vs_emulator(ks, plane, epi):
+    """The bf16x3 epilogues of conv16v4 that no other test launches -- KS 5 at the
+    15 x 15 plane, KS 3 at all four compile-time planes (30 x 30: two 30 x 15
+    tiles) -- on the same emulator oracle and bound; J = 6 leaves the second
+    block of R = 5 output j-planes partial."""
+    _conv16_x3_vs_emulator(0, plane, epi, ks, (1, 2, 6))
+
+
+def _conv16_x3_vs_emulator(grp, plane, epi, ks, vij):
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
     from tests import emu_ext
     torch.manual_seed(3)
-    ks = 5
-    V, I, J = 2, 6, 5
+    V, I, J = vij
     shp = (V, I, J, plane, plane)
     xs = (grp,) if grp else ()
     x = torch.randn(xs + shp + (16,), device="cuda")
@@ -159,7 +172,10 @@ def _unpair(p):
 @pytest.mark.parametrize("cin,cout,k,stride,pad,res,relu,shape", [
     (256, 256, 3, 1, 1, False, True, (3, 25, 25)), (1024, 256, 1, 1, 0, False, True, (2, 25, 25)),
     (256, 1024, 1, 1, 0, True, True, (2, 25, 25)), (64, 64, 3, 1, 1, False, True, (2, 37, 29)),
-    (128, 128, 3, 2, 1, False, True, (2, 50, 50)), (512, 1024, 1, 2, 0, False, False, (1, 50, 50))])
+    (128, 128, 3, 2, 1, False, True, (2, 50, 50)), (512, 1024, 1, 2, 0, False, False, (1, 50, 50))] +
+    # tile rows TM 4 / 5 / 6 at the 64 / 128 / 256-column tiles (M = 256 CUs x 16 TM pixels, see
+    # tests/test_gpu_kernels.py test_conv2d_nhwc_v3)
+    [(128, cout, 3, 1, 1, False, True, (1, 128, wd)) for wd in (128, 160, 192) for cout in (64, 128, 256)])
 def test_conv2d_x3_vs_fp64(cin, cout, k, stride, pad, res, relu, shape):
     """conv2d_nhwc_v3 X3 mode: [hi | lo] bf16 pairs in and out, acc = X_hi W_hi +
     X_lo W_hi + X_hi W_lo, fp32 bias / residual / ReLU: the fp32 conv to ~1e-5."""
