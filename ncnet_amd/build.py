@@ -122,8 +122,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, v
         hip_flags = [f for f in hip_flags if f != "-O3"] + ["-O1", "-g", "-DNCNET_DEBUG=1"]
     elif variant == "asan":
         # only the host side is sanitized and built -O1 -g; the device code keeps
-        # the release flags (the inline-asm LDS-DMA of csrc/common.h needs the
-        # optimizer to keep its LDS address in a scalar register)
+        # the release flags (without NCNET_DEBUG the inline-asm LDS-DMA of
+        # csrc/lds_dma.h needs the optimizer to keep its LDS address in a scalar
+        # register; see lds_m0 there)
         hip_flags += ["-Xarch_host", "-O1", "-Xarch_host", "-g", "-Xarch_host", "-fsanitize=address",
                       "-Xarch_host", "-fno-omit-frame-pointer"]
 

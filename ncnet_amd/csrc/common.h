@@ -92,23 +92,8 @@ __device__ __forceinline__ float s162f(uint16_t x) {
   else return (float)__builtin_bit_cast(__bf16, x);
 }
 
-// LDS-DMA of 16 B per lane (global_load_lds_dwordx4) issued from inline asm.
-// The compiler's waitcnt pass cannot prove that an LDS-DMA misses a later
-// ds_read_b64_tr_b16 (intrinsic reads carry no alias info), so with the builtin
-// it drains EVERY in-flight DMA (s_waitcnt vmcnt(0)) before the first
-// transposed read -- the next step's prefetch is serialised with the compute.
-// Issued from asm the DMA is invisible to that pass; the kernel then owns the
-// wait: `s_waitcnt vmcnt(..)` + s_barrier (asm_barrier_vm below) before reading
-// what landed.  (Extra in-flight asm ops only make the compiler's own vmcnt
-// waits stricter, never weaker: completion is in issue order.)  M0 is set here;
-// kernels using this issue no other M0-based instruction.
-__device__ __forceinline__ void dma16_lds(const void* gsrc, const void* lds_dst) {
-  const uint32_t l = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)lds_dst;
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(l) : "memory", "m0");
-}
-// Workgroup barrier that first waits for ALL of this wave's vector-memory ops
-// (incl. asm LDS-DMAs) and LDS ops.
-__device__ __forceinline__ void asm_barrier_vm0() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// LDS-DMA helpers, counted waits, static_for and the LDS swizzles
+#include "lds_dma.h"
 
 __device__ __forceinline__ bf16x8 lds_read16(const char* lds_base, uint32_t byte_off) {
   return *(const bf16x8*)(lds_base + byte_off);
@@ -143,6 +128,32 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblocks) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- staged (k, l) plane geometry of the Conv4d kernels (fwd and wgrad) ----
+// Element offset of plane (v, i, j) of a channels-last [V, I, J, K, L, C]
+// volume; G is any geometry struct with I, J, K, L (ConvGeom, WGeom).
+template <class G>
+__device__ __forceinline__ size_t plane_offset(const G& g, int v, int i, int j, int C) {
+  return ((((size_t)v * g.I + i) * g.J + j) * (size_t)g.K * g.L) * C;
+}
+// Row stride (32-byte voxels) of a staged plane with tl output columns: the
+// KS - 1 halo columns rounded up to 8 voxels (tl + 8 for KS 3 / 5 / 7), so a
+// 16-voxel tile that wraps to the next row jumps a whole 256-B bank period and
+// every ds_read_b128 / transposed-read lane group stays conflict-free (a
+// tl + KS - 1 stride cost ~1/3 extra LDS cycles).
+__host__ __device__ constexpr int row_stride(int tl, int ks) { return tl + ((ks - 1 + 7) / 8) * 8; }
+// Output tile of a (K, L) plane.  Forward (split = true): the whole plane when
+// it fits (<= 25 x 25 output); planes up to 32 x 32 (--image_size 480: 30 x 30)
+// split into two K x ceil(L / 2) tiles (a 25 x 25 tile on a 30 x 30 plane left
+// 4 tiles of 2500 voxel slots for 900 voxels); else 25 x 25 tiles (InLoc-size
+// planes).  The weight gradient (split = false) uses the tail alone.
+static inline void pick_tile(int K, int L, int& tk, int& tl, bool split = true) {
+  if (split && (K > 25 || L > 25) && K <= 32 && L <= 32) { tk = K; tl = (L + 1) / 2; return; }
+  tk = K <= 25 ? K : 25;
+  tl = L <= 25 ? L : 25;
+  // keep TK*TL <= 640 (MAXT * 8 waves * 16 voxels)
+  while (tk * tl > 640) { if (tl > tk) --tl; else --tk; }
+}
 
 // Runtime value -> template argument, the one way launchers select a kernel:
 // dispatch_int<Vs...>(v, f) calls f(std::integral_constant<int, V>{}) for the V

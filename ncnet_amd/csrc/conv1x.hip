@@ -41,14 +41,6 @@
 
 namespace ncnet {
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void xstatic_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    xstatic_for<B + 1, E>(f);
-  }
-}
-
 // EPI1X_X3 (| with either): the fp32-accurate bf16x3 layer of nc_precision='fp32'
 // training: three phases per item, (X_hi, W_hi), (X_lo, W_hi), (X_hi, W_lo),
 // into the same accumulators (X_lo = Xp + xlo, Wa = [hi set; lo set]); the
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
   constexpr int XOFF = PH == 3 ? 2 * NT * 1024 : C::XOFF;   // both weight sets precede the planes
   constexpr int S = R + KS - 1;          // input j-planes per di = one step
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int njb = (J + R - 1) / R;
@@ -201,20 +193,11 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
     for (int u = 0; u < S; ++u) {
       const int jp = jb * R - P + u;
       const bool pv = iv && jp >= 0 && jp < J;
-      const uint64_t pb = (uint64_t)(pv ? xrow + (size_t)jp * PPL : Xp);
-      typedef int i32x4v __attribute__((ext_vector_type(4)));
-      i32x4v rs;
-      rs[0] = (int)(uint32_t)pb;
-      rs[1] = (int)((uint32_t)(pb >> 32) & 0xffffu);
-      rs[2] = pv ? PPL * 2 : 0;
-      rs[3] = 0x00020000;
+      const i32x4 rs = make_rsrc<false>(pv ? xrow + (size_t)jp * PPL : Xp, pv ? PPL * 2 : 0);
 #pragma unroll
       for (int m = 0; m < JPW; ++m) {
         const uint32_t d = slot + (uint32_t)(u * C::SLOTB) + doff[m];
-        if (jon[m])
-          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(dvo[m]), "s"(rs),
-                       "s"(d)
-                       : "memory", "m0");
+        if (jon[m]) bdma16_lds(rs, dvo[m], d);
       }
     }
   };
@@ -259,7 +242,7 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
     int n_jb = c_jb, n_ti = c_ti, n_tv = c_tv;         // item of step n + 1
     if (last) advance(n_jb, n_ti, n_tv);
     // this step's planes landed (issued one step ago); the previous step's reads are done
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    asm_barrier_vm0();
     issue(n + 1, n_jb, n_ti, n_tv);
     if constexpr (EP == EPI1X_MASK) {
       // the item's last step: fetch the ReLU mask of its outputs now, so the
@@ -290,7 +273,7 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
 #pragma unroll
       for (int dj = 0; dj < KS; ++dj) A[dj] = lds_read16(smem, C::WOFF + (wset + di * KS + dj) * 1024 + lane * 16);
       const uint32_t sb = (uint32_t)((n & 1) * S * C::SLOTB);
-      xstatic_for<0, S>([&](auto sc) {
+      static_for<0, S>([&](auto sc) {
         constexpr int s = decltype(sc)::value;   // plane j' = j0 - P + s
         const int jp = j0 - P + s;
         if (jp >= 0 && jp < J) {
@@ -306,12 +289,12 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
             constexpr int tt = decltype(tc)::value;
             B[tt % (PD + 1)] = cat4u(lds_read_tr16u(smem, a0 + tt * NW * 32), lds_read_tr16u(smem, a1 + tt * NW * 32));
           };
-          xstatic_for<0, (PD < MAXT ? PD : MAXT)>([&](auto tc) { load_b(tc); });
+          static_for<0, (PD < MAXT ? PD : MAXT)>([&](auto tc) { load_b(tc); });
           __builtin_amdgcn_sched_group_barrier(0x100, 2 * (PD < MAXT ? PD : MAXT), 0);
-          xstatic_for<0, MAXT>([&](auto tc) {
+          static_for<0, MAXT>([&](auto tc) {
             constexpr int tt = decltype(tc)::value;
             if constexpr (tt + PD < MAXT) load_b(std::integral_constant<int, tt + PD>{});
-            xstatic_for<dlo, dhi + 1>([&](auto dc) {
+            static_for<dlo, dhi + 1>([&](auto dc) {
               constexpr int dj = decltype(dc)::value;
               acc[s - dj][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                   A[dj], __builtin_bit_cast(bf16x8, B[tt % (PD + 1)]), acc[s - dj][tt], 0, 0, 0);
@@ -365,7 +348,7 @@ __global__ __launch_bounds__(512, 1) void conv1x16_kernel(const bf16* __restrict
     }
     c_jb = n_jb; c_ti = n_ti; c_tv = n_tv;
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may land after the workgroup ends
+  dma_wait<0>();   // no LDS-DMA may land after the workgroup ends
 #endif
 }
 
@@ -436,7 +419,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
   using C = W1X<KS, K, L>;
   constexpr int P = C::P, NT = C::NT, NW = C::NW, LP = C::LP, PPL = C::PPL, NCOL = C::NCOL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int th = wave & 1, cq = wave >> 1;
@@ -448,27 +431,19 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
   auto dma_x = [&](int v, int i, int di, int jc, int half) {   // X1 plane (v, i+di-P, jc) -> its ring slot
     const int ip = i + di - P;
     const bool pv = ip >= 0 && ip < I && jc >= 0 && jc < J;
-    const uint64_t pb = (uint64_t)(pv ? X1 + ((size_t)(v * I + ip) * J + jc) * PPL : X1);
-    typedef int i32x4v __attribute__((ext_vector_type(4)));
-    i32x4v rs;
-    rs[0] = (int)(uint32_t)pb;
-    rs[1] = (int)((uint32_t)(pb >> 32) & 0xffffu);
-    rs[2] = pv ? PPL * 2 : 0;            // an absent plane reads as zeros
-    rs[3] = 0x00020000;
+    // an absent plane reads as zeros
+    const i32x4 rs = make_rsrc<false>(pv ? X1 + ((size_t)(v * I + ip) * J + jc) * PPL : X1, pv ? PPL * 2 : 0);
     const uint32_t d = __builtin_amdgcn_readfirstlane(
         lds0 + (uint32_t)(C::XOFF + (di * NCOL + (jc + P + NCOL) % NCOL) * C::XS + half * 1024));
     const uint32_t vo = (uint32_t)(half * 1024 + lane * 16);
-    if (half < C::NXD - 1 || lane < C::XDMAL)
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(vo), "s"(rs), "s"(d)
-                   : "memory", "m0");
+    if (half < C::NXD - 1 || lane < C::XDMAL) bdma16_lds(rs, vo, d);
   };
   auto issue_g = [&](int t, int buf) {                          // D plane t (K rows of L voxels) -> buffer
     const bf16* src = D + (size_t)t * K * L * 16;
     for (int k = wave; k < K; k += NW) {
       const uint32_t d = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(C::GOFF + buf * C::GBYTES + (C::GM + k * LP) * 32));
       const bf16* a = src + (size_t)k * L * 16 + lane * 8;
-      if (lane < L * 2)
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(a), "s"(d) : "memory", "m0");
+      if (lane < L * 2) dma16_lds(a, d);
     }
   };
   auto issue_x_all = [&](int t) {                               // the KS x KS neighbourhood of step t
@@ -505,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
   // issued (12 % of the MFMAs and transposed reads of a full 27-chunk sweep)
   auto body = [&](auto thc, auto cqc, uint32_t xa0, uint32_t xa1, uint32_t ga) {
     constexpr int TH = decltype(thc)::value, CQ = decltype(cqc)::value;
-    xstatic_for<0, C::NU>([&](auto uc) {
+    static_for<0, C::NU>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
       constexpr int chunk = CQ + 4 * u;
       if constexpr (chunk < C::NQC) {
@@ -513,7 +488,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
         const u32x4 A0 = cat4u(*(const u32x2*)(smem + xa0 + 256 * u), *(const u32x2*)(smem + xa0 + 256 * u + 32));
         u32x4 A1 = A0;
         if constexpr (TWO) A1 = cat4u(*(const u32x2*)(smem + xa1 + 256 * u), *(const u32x2*)(smem + xa1 + 256 * u + 32));
-        xstatic_for<0, C::NTW>([&](auto tc) {
+        static_for<0, C::NTW>([&](auto tc) {
           constexpr int tt = decltype(tc)::value;
           constexpr int tap = C::NTW * TH + tt;
           constexpr int s = (tap / KS) * LP + tap % KS;
@@ -565,7 +540,7 @@ __global__ __launch_bounds__(512, 1) void wgrad1x16_kernel(const bf16* __restric
 #pragma unroll
     for (int turn = 0; turn < 4; ++turn) {
       if (turn == CQ) {
-        xstatic_for<0, C::NTW>([&](auto tc) {
+        static_for<0, C::NTW>([&](auto tc) {
           constexpr int tt = decltype(tc)::value;
           constexpr int tap = C::NTW * TH + tt;
           if constexpr (tap < NT) {

@@ -23,10 +23,7 @@
 namespace ncnet {
 
 namespace cv {
-constexpr int BK = 64;
-// chunk ^ ((row >> 1) & 7): the 16 rows of a ds_read_b128 lane group land on 16
-// distinct 16-B bank slots (chunk ^ (row & 7) put rows r and r + 8 on one slot)
-__device__ __forceinline__ uint32_t toff(int row, int chunk) { return (uint32_t)(row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4)); }
+constexpr int BK = 64;   // 128-byte LDS rows at toff (lds_dma.h)
 }  // namespace cv
 
 struct Conv2dArgs {
@@ -235,15 +232,8 @@ __global__ __launch_bounds__(256, 2) void conv2d_nhwc_kernel(Conv2dArgs p) {
 __device__ const uint4 g_zero16 = {0u, 0u, 0u, 0u};
 
 namespace cv2 {
-constexpr int BK = 32;
-__device__ __forceinline__ int swz(int r) { return (r & 1) ^ ((r >> 1) & 2); }
-__device__ __forceinline__ uint32_t roff(int row, int chunk) { return (uint32_t)(row * 64 + ((chunk ^ swz(row)) << 4)); }
+constexpr int BK = 32;   // 64-byte LDS rows at roff / swz (lds_dma.h)
 }  // namespace cv2
-
-template <int N>
-__device__ __forceinline__ void c2_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // NW waves (4: 2x2 / 4x1 of 64x64 / 32x64; 8: 4x2 of 64x64 for the 256x128
 // tile, 85 FLOP per L2 byte instead of 64; 8: 4x2 of 64x128 for the 256x256
@@ -334,9 +324,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv2d_nhwc_v2_kernel(Conv2dA
   for (int ks = 0; ks < nk; ++ks) {
     // stage ks landed once at most the stages issued after it remain in flight
     const int after = min(NS - 2, nk - 1 - ks);
-    if (NS >= 4 && after >= 2) c2_wait_barrier<2 * PER>();
-    else if (after >= 1) c2_wait_barrier<PER>();
-    else c2_wait_barrier<0>();
+    if (NS >= 4 && after >= 2) dma_wait_barrier<2 * PER>();
+    else if (after >= 1) dma_wait_barrier<PER>();
+    else dma_wait_barrier<0>();
     if (ks + NS - 1 < nk) issue(ks + NS - 1, (buf + NS - 1) % NS);   // the buffer consumed at ks - 1
     const char* As = smem + buf * STAGE;
     const char* Bs = As + BM * 64;
@@ -385,9 +375,6 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void conv2d_nhwc_v2_kernel(Conv2dA
 // ===========================================================================
 namespace cv3 {
 constexpr int NS = 3;
-// chunk ^ ((row >> 1) & 7): the 16 rows of a ds_read_b128 lane group land on 16
-// distinct 16-B bank slots (chunk ^ (row & 7) put rows r and r + 8 on one slot)
-__device__ __forceinline__ uint32_t toff(int row, int chunk) { return (uint32_t)(row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4)); }
 template <int TM, int TN>
 struct Geo {
   static constexpr int BM = 16 * TM, BN = 64 * TN;
@@ -401,11 +388,6 @@ struct Geo {
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 }  // namespace cv3
-
-template <int N>
-__device__ __forceinline__ void c3_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // X3 (fp32-accurate "bf16x3" trunk, FrozenResNetPlan dtype float32): X, R, Y
 // hold [hi | lo] bf16 channel pairs (Cx = 2 Cin), the GEMM runs Ck = 3 Cin
@@ -503,8 +485,8 @@ __global__ __launch_bounds__(512, 1) void conv2d_nhwc_v3_kernel(Conv2dArgs p) {
   const int kc = kg * 4 + fq;      // this lane's 16-B chunk of the 64-deep stage
   int buf = 0;
   for (int ks = 0; ks < nk; ++ks) {
-    if (ks + 1 < nk) c3_wait_barrier<PER>();   // stage ks landed; ks + 1 may still fly
-    else c3_wait_barrier<0>();
+    if (ks + 1 < nk) dma_wait_barrier<PER>();   // stage ks landed; ks + 1 may still fly
+    else dma_wait_barrier<0>();
     if (ks + NS - 1 < nk) issue(ks + NS - 1, (buf + NS - 1) % NS);   // into the buffer consumed at ks - 1
     const char* As = smem + buf * G::STAGE;
     const char* Bs = As + BM * 128;

@@ -69,10 +69,6 @@ __device__ __forceinline__ TileId decode_tile(const ConvGeom& g) {
   return t;
 }
 
-__device__ __forceinline__ size_t plane_offset(const ConvGeom& g, int v, int i, int j, int C) {
-  return ((((size_t)v * g.I + i) * g.J + j) * (size_t)g.K * g.L) * C;
-}
-
 // Epilogue for a [16 co x 16 voxel] accumulator tile: lane holds co = 4(l>>4)+r
 // of voxel (l & 15).
 // nt: streaming (non-temporal) stores -- the volumes written here (0.1-1.6 GB)
@@ -178,7 +174,7 @@ __global__ __launch_bounds__(512, KS >= 7 ? 1 : 2) void conv16v2_fwd_kernel(cons
     g.K = g.L = g.TK = g.TL = CT;
     g.nkt = g.nlt = 1;
     g.PR = g.RW = CT + KS - 1;
-    g.RS = CT + ((KS - 1 + 7) / 8) * 8;
+    g.RS = row_stride(CT, KS);
   }
   constexpr int P = KS / 2;
   constexpr int NT = KS * KS;
@@ -440,14 +436,6 @@ __global__ __launch_bounds__(512, KS >= 7 ? 1 : 2) void conv16v2_fwd_kernel(cons
 //  * 8 waves x 5 voxel tiles, 1 workgroup per CU (128 KB LDS for KS = 5).
 // Plane geometry (RS = TL + 8, halo zero-fill, row DMA) as conv16v2.
 // ===========================================================================
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
-
 template <int KS, int R, int EPI>
 __global__ __launch_bounds__(512, 1) void conv16v3_fwd_kernel(const bf16* __restrict__ X, const u32x4* __restrict__ Wp,
                                                               const float* __restrict__ bias,
@@ -633,11 +621,10 @@ __global__ __launch_bounds__(512, 1) void conv16v3_fwd_kernel(const bf16* __rest
 //    2q + 1) differ by one voxel or by one row wrap, two base sets cover both;
 //  * three plane buffers, DMA two planes ahead, and a counted
 //    `s_waitcnt vmcnt(N)` before each step's barrier waits for the plane (and
-//    weights) that step reads but leaves the next plane's DMA in flight.  Every
-//    wave issues a FIXED number of DMA instructions per plane and per weight
-//    slot (rows / slots it does not own go to a trash KiB of LDS) so N is a
-//    compile-time count; buffer-resource DMAs return zeros out of range, so the
-//    halo is written by the DMA (no zero fill, no exec masks).
+//    weights) that step reads but leaves the next plane's DMA in flight (the
+//    fixed-count contract of lds_dma.h: rows / slots a wave does not own go to
+//    a trash KiB of LDS); buffer-resource DMAs return zeros out of range, so
+//    the halo is written by the DMA (no zero fill, no exec masks).
 // LDS (KS = 5, 25 x 25): 65 KB weights + 3 x 30.6 KB planes + 1 KB = 156 KB.
 // ===========================================================================
 // does step s of a di issue a weight slot (slot s - R of di + 1, or slot KS - 1 of di at s = 0)?
@@ -665,7 +652,7 @@ __global__ __launch_bounds__(512, 1) void conv16v4_fwd_kernel(const bf16* __rest
   constexpr int MT = SPLIT ? NTILE / NW : MAXT;   // whole tiles per wave
   constexpr int TS = NW * MT;                      // the split tile (SPLIT)
   constexpr int S = R + KS - 1;              // input j-planes per di
-  constexpr int RS = TL + 8;                 // row stride (voxels): a wrapping tile jumps one 256-B bank period
+  constexpr int RS = row_stride(TL, KS);     // row stride (voxels): a wrapping tile jumps one 256-B bank period
   constexpr int PR = TK + KS - 1;            // staged rows
   constexpr int PLANE = PR * RS * 32;
   // LDS: weights first (so every fragment read is a base VGPR + a 16-bit
@@ -803,7 +790,7 @@ __global__ __launch_bounds__(512, 1) void conv16v4_fwd_kernel(const bf16* __rest
       constexpr int s = decltype(sc)::value;
       // DMAs younger than plane n: the previous step's weight slot (if any) and plane n + 1
       constexpr int YOUNGER = RPW + (v4_wstep(s == 0 ? S - 1 : s - 1, R) ? WPW : 0);
-      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(YOUNGER) : "memory");
+      dma_wait_lds_barrier<YOUNGER>();
       if constexpr (v4_wstep(s, R)) {
         if constexpr (s >= R) issue_w(dv + 1 < nd ? dv + 1 : dv, s - R, dv + 1 < nd);
         else issue_w(dv, KS - 1, dv > 0);
@@ -891,7 +878,7 @@ __global__ __launch_bounds__(512, 1) void conv16v4_fwd_kernel(const bf16* __rest
       ++n;
     });
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may land after the workgroup ends
+  dma_wait<0>();   // no LDS-DMA may land after the workgroup ends
 
   const size_t nvox_all = (size_t)g.V * g.I * g.J * g.K * g.L;
   auto out_vox_t = [&](int r, int tile, size_t& vox) -> bool {
@@ -1128,7 +1115,7 @@ static bool v4_launch(int KS, int K, int L, int tk, int tl, int epi, dim3 grid, 
       constexpr int KSV = decltype(ksc)::value, TK = decltype(kc)::value, TL = TK == 30 ? 15 : TK;
       constexpr int R = 5, NQ = (KSV * KSV + 1) / 2;
       if (tk != TK || tl != TL) return;
-      const size_t lds = 3 * (size_t)(TK + KSV - 1) * (TL + ((KSV - 1 + 7) / 8) * 8) * 32 + (size_t)KSV * NQ * 1024 + 1024;
+      const size_t lds = 3 * (size_t)(TK + KSV - 1) * row_stride(TL, KSV) * 32 + (size_t)KSV * NQ * 1024 + 1024;
       hit = dispatch_int<EPI_BIAS_RELU, EPI_MASK, EPI_BIAS_RELU | EPI_X3, EPI_MASK | EPI_X3>(e4, [&](auto ec) {
         hipLaunchKernelGGL((conv16v4_fwd_kernel<KSV, R, decltype(ec)::value, TK, TL>), grid, block, lds, stream, x, w,
                            bias, m, y, g);
@@ -1136,20 +1123,6 @@ static bool v4_launch(int KS, int K, int L, int tk, int tl, int epi, dim3 grid, 
     });
   });
   return hit;
-}
-
-// Tile choice: the whole (k,l) plane when it fits (<= 25 x 25 output); planes
-// up to 32 x 32 (--image_size 480: 30 x 30) split into two K x ceil(L / 2)
-// tiles (a 25 x 25 tile on a 30 x 30 plane left 4 tiles of 2500 voxel slots
-// for 900 voxels); else 25 x 25 tiles (InLoc-size planes).
-static void pick_tile(int K, int L, int& tk, int& tl) {
-  if (K > 25 || L > 25) {
-    if (K <= 32 && L <= 32) { tk = K; tl = (L + 1) / 2; return; }
-  }
-  tk = K <= 25 ? K : 25;
-  tl = L <= 25 ? L : 25;
-  // keep TK*TL <= 640 (MAXT * 8 waves * 16 voxels)
-  while (tk * tl > 640) { if (tl > tk) --tl; else --tk; }
 }
 
 // output j-tiles per workgroup of the group-plane conv
@@ -1176,10 +1149,7 @@ extern "C" int ncnet_conv16_fwd(const void* X, const void* Wp, const float* bias
   if (g.RW > 32) return -1;   // one LDS-DMA wave-instruction per staged row
   const bool x3 = (epi & EPI_X3) != 0;
   if (x3 && !((KS == 5 || KS == 3) && ((epi & ~EPI_X3) == EPI_BIAS_RELU || (epi & ~EPI_X3) == EPI_MASK))) return -2;
-  // Row stride RS = TL + 8: a 16-voxel tile that wraps to the next row then
-  // jumps 256 B (the full 64-bank period), so every ds_read_b128 lane group
-  // stays conflict-free (a TL + KS - 1 stride cost ~1/3 extra LDS cycles).
-  g.RS = tl + ((KS - 1 + 7) / 8) * 8;
+  g.RS = row_stride(tl, KS);
   const int nq = (KS * KS + 1) / 2;
   const bf16* x = (const bf16*)X; const u32x4* w = (const u32x4*)Wp; const bf16* m = (const bf16*)M; bf16* y = (bf16*)Y;
 
@@ -1246,7 +1216,7 @@ extern "C" int ncnet_conv16_blk_fwd(const void* X, const void* Wp, const float* 
   g.xlo = xlo;
   if (x3 && KS != 5 && KS != 3) return -2;
   if (g.RW > 32) return -1;
-  g.RS = tl + ((KS - 1 + 7) / 8) * 8;
+  g.RS = row_stride(tl, KS);
   g.nib = cdiv(I, 4); g.njb = cdiv(J, 4);
   g.relu = relu;
   const int nq = (KS * KS + 1) / 2;

@@ -23,14 +23,6 @@
 
 namespace ncnet {
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void wstatic_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    wstatic_for<B + 1, E>(f);
-  }
-}
-
 struct WGeom {
   int V, I, J, K, L;
   int TK, TL, nkt, nlt;
@@ -65,10 +57,6 @@ __device__ __forceinline__ void next_item(const WGeom& g, Item& r) {
   if (++r.i < g.I) return;
   r.i = 0;
   ++r.v;
-}
-
-__device__ __forceinline__ size_t plane_off(const WGeom& g, int v, int i, int j, int C) {
-  return ((((size_t)v * g.I + i) * g.J + j) * (size_t)g.K * g.L) * C;
 }
 
 // ===========================================================================
@@ -142,8 +130,8 @@ __global__ __launch_bounds__(512, 2) void wgrad16v2_kernel(const bf16* __restric
     // Stage X plane rows (corner (k0-P, l0-P)) and G tile rows (corner (k0, l0)):
     // in-volume 16-byte chunks by LDS-DMA, everything else of the row zeroed
     // with ds_write (tile positions differ per item, so no stale halo survives).
-    const bf16* xp = X + plane_off(g, r.v, ii, jj, 16);
-    const bf16* gp = G + plane_off(g, r.v, r.i, r.j, 16);
+    const bf16* xp = X + plane_offset(g, r.v, ii, jj, 16);
+    const bf16* gp = G + plane_offset(g, r.v, r.i, r.j, 16);
     const size_t ext = (size_t)g.V * g.I * g.J * g.K * g.L * 16;
     (void)ext;
     {
@@ -439,10 +427,10 @@ __global__ __launch_bounds__(512, 1) void wgrad16v3_kernel(const bf16* __restric
           // last tap (afr) x this group's di range: the G fragments of those di
           // are already in registers (bfr), selected by a wave-uniform branch
           // on the group so every fragment index stays compile-time
-          wstatic_for<1, 4>([&](auto tc) {
+          static_for<1, 4>([&](auto tc) {
             constexpr int TGC = decltype(tc)::value;
             if (tg == TGC) {
-              wstatic_for<0, EXP>([&](auto ec) {
+              static_for<0, EXP>([&](auto ec) {
                 constexpr int e = decltype(ec)::value;
                 constexpr int d = (TGC - 1) * EXP + e;
                 if constexpr (d < KS && d < TGC * EXP) accx[e] = mfma16u(afr, bfr[u & 1][d], accx[e]);
@@ -513,7 +501,7 @@ struct W4C {
   static constexpr int VT = NC32 * 32;
   static constexpr int NCH0 = (NC32 + 1) / 2, NCH1 = NC32 / 2;   // chunks of half 0 / half 1
   static constexpr int NCH = NCH0;                       // the larger
-  static constexpr int RS = L + 8, RW = L + KS - 1;
+  static constexpr int RS = row_stride(L, KS), RW = L + KS - 1;
   static constexpr int PR = (VT - 1) / L + 2 + KS - 1;   // staged X rows
   static constexpr int XB = PR * RS * 32, GB = VT * 32;
   static constexpr int NS = 2 * P + 3;                   // G ring slots (2 steps ahead)
@@ -528,23 +516,6 @@ struct W4C {
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-// 16-B-per-lane buffer load into LDS from asm (see dma16_lds in common.h):
-// out-of-range offsets land as zeros.
-typedef int i32x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4v make_rsrc(const void* base, uint32_t nbytes) {
-  const uint64_t b = (uint64_t)base;
-  i32x4v r;
-  r[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  r[1] = __builtin_amdgcn_readfirstlane((int)((uint32_t)(b >> 32) & 0xffffu));
-  r[2] = __builtin_amdgcn_readfirstlane((int)nbytes);
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void bdma16_lds(const i32x4v& rs, uint32_t voff, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "s"(lds)
-               : "memory", "m0");
-}
-
 template <int KS, int K, int L, int TG, int NCHH>
 __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const bf16* __restrict__ G,
                                                float* __restrict__ part, float* __restrict__ partb, const W3Geom& g,
@@ -555,7 +526,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
   constexpr int RS = C::RS, PR = C::PR, XB = C::XB, GB = C::GB;
   constexpr int RPW = C::RPW, GPW = C::GPW, GQ = C::GQ;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   const int lane = threadIdx.x & 63;
   const bool center_blk = dj == P;
   constexpr int XLO = TG == 0 ? KS : (TG - 1) * EXP;              // di range of the last tap (NT - 1)
@@ -609,7 +580,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
   auto issue_x = [&]() {
     const bool live = xl_n < nsteps;
     const bf16* xp = live ? X + xl_base + (size_t)xl_ii * pstride : X;
-    const i32x4v rs = make_rsrc(xp, live ? (uint32_t)(K * L * 32) : 0u);
+    const i32x4 rs = make_rsrc(xp, live ? (uint32_t)(K * L * 32) : 0u);
     const uint32_t xb = lds0 + C::XOFF + (uint32_t)((xl_n % 3) * XB);
 #pragma unroll
     for (int m = 0; m < RPW; ++m) {
@@ -643,7 +614,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
   auto issue_g = [&]() {
     const bool live = gl_m < nsteps;
     const bf16* gp = live ? G + gl_base + (size_t)gl_gi * pstride : G;
-    const i32x4v rs = make_rsrc(gp, live ? (uint32_t)gl_nvb : 0u);
+    const i32x4 rs = make_rsrc(gp, live ? (uint32_t)gl_nvb : 0u);
     const uint32_t gb = lds0 + C::GOFF + (uint32_t)((gl_m % NS) * GB);
 #pragma unroll
     for (int m = 0; m < GPW; ++m) {
@@ -686,7 +657,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
   for (int n = 0; n < nsteps; ++n) {
     // plane n and G tile n + P landed (issued two steps ago); only the previous
     // step's RPW + GPW DMAs may still be in flight; previous step's reads done
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(RPW * XI + GPW) : "memory");
+    dma_wait_lds_barrier<RPW * XI + GPW>();
     issue_x();
     issue_g();
     const uint32_t xb = (uint32_t)(C::XOFF + (n % 3) * XB);
@@ -720,7 +691,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
     for (int d = 0; d < KS; ++d) load_b(std::integral_constant<int, 0>{}, d);
     load_a(std::integral_constant<int, 0>{});
     __builtin_amdgcn_sched_group_barrier(0x100, 2 * KS + 2, 0);
-    wstatic_for<0, NKG>([&](auto kc) {
+    static_for<0, NKG>([&](auto kc) {
       constexpr int k = decltype(kc)::value;
       constexpr int u = k / NM, m = k % NM;
       // reads issued in this group: the next group's X fragment, and (m < KS)
@@ -733,7 +704,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
 #pragma unroll
         for (int d = 0; d < KS; ++d) acc[m][d] = mfma16u(afr[k & 1], bfr[u & 1][d], acc[m][d]);
       } else {
-        wstatic_for<XLO, XHI>([&](auto dc) {
+        static_for<XLO, XHI>([&](auto dc) {
           constexpr int d = decltype(dc)::value;
           accx[d - XLO] = mfma16u(afr[k & 1], bfr[u & 1][d], accx[d - XLO]);
         });
@@ -752,7 +723,7 @@ __device__ __forceinline__ void wgrad16v4_body(const bf16* __restrict__ X, const
       if (cc < c_hi) set_tile(cc);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may land after the workgroup ends
+  dma_wait<0>();   // no LDS-DMA may land after the workgroup ends
 
   // D[row = ci = 4(l>>4)+r][col = co = l&15]
   const int row = grp * 2 + half;
@@ -946,16 +917,10 @@ __global__ __launch_bounds__(512, 1) void wgrad16p_kernel(const bf16* __restrict
 
 using namespace ncnet;
 
-static void pick_tile_w(int K, int L, int& tk, int& tl) {
-  tk = K <= 25 ? K : 25;
-  tl = L <= 25 ? L : 25;
-  while (tk * tl > 640) { if (tl > tk) --tl; else --tk; }
-}
-
 static WGeom make_wgeom(int V, int I, int J, int K, int L, int KS, int ngroups) {
   WGeom g;
   g.V = V; g.I = I; g.J = J; g.K = K; g.L = L;
-  pick_tile_w(K, L, g.TK, g.TL);
+  pick_tile(K, L, g.TK, g.TL, false);   // no split of wide planes: 25 x 25 tiles
   g.nkt = cdiv(K, g.TK); g.nlt = cdiv(L, g.TL);
   g.PR = g.TK + KS - 1; g.RS = g.TL + KS - 1; g.RW = g.RS;
   g.nitems = V * I * J * g.nkt * g.nlt;
@@ -974,9 +939,7 @@ extern "C" int ncnet_wgrad16(const void* X, const void* G, float* part, float* p
   dim3 grid((unsigned)((dj_center == 2 ? 1 : KS * KS) * ngroups));
   const bf16* x = (const bf16*)X; const bf16* gg = (const bf16*)G;
   if (g.RW > 32 || g.TL > 32) return -1;   // one wave-instruction per staged row
-  // row stride TL + 8: a row wrap inside an 8-voxel read group jumps 256 B
-  // (bank period), keeping the transposed reads conflict-free
-  g.RS = g.TL + ((KS - 1 + 7) / 8) * 8;
+  g.RS = row_stride(g.TL, KS);
   if (g.PR * g.RS * 32 > 65535) return -1;  // 16-bit voxel offset table
   size_t lds = (size_t)g.PR * g.RS * 32 + (size_t)nv32 * 32 + (size_t)nv32 * 2;
   dim3 block(512);
@@ -994,7 +957,7 @@ extern "C" int ncnet_wgrad16p(const void* X, const void* G, float* part, float* 
   if (K > 25 || L > 25) return -1;
   if (ngg != 1 && ngg != 2) return -3;
   WGeom g = make_wgeom(V, I, J, K, L, KS, ngroups);
-  g.RS = L + ((KS - 1 + 7) / 8) * 8;        // row wrap jumps 256 B (conflict-free transposed reads)
+  g.RS = row_stride(L, KS);
   g.PR = K + KS - 1;
   if (L + KS - 1 > g.RS || g.PR * g.RS * 32 > 65535) return -1;
   const int nv32 = (K * L + 31) & ~31;
@@ -1040,7 +1003,7 @@ extern "C" int ncnet_wgrad16v3(const void* X, const void* G, float* part, float*
   g.ntl = cdiv(KL, 320);
   g.VT = ((cdiv(KL, g.ntl) + 63) / 64) * 64;
   g.RW = L + KS - 1;
-  g.RS = L + ((KS - 1 + 7) / 8) * 8;
+  g.RS = row_stride(L, KS);
   g.PR = (g.VT - 1) / L + 2 + KS - 1;
   g.ncols = V * J * g.ntl;
   g.cpg = cdiv(g.ncols, ngroups);

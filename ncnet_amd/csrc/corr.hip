@@ -274,15 +274,8 @@ __device__ const uint4 g_corr_zero16 = {0u, 0u, 0u, 0u};
 namespace cg2 {
 constexpr int BM = 256, BN = 128, NW = 8, BK = 32, GM = 4;
 constexpr int APW = BM / (16 * NW), BPW = BN / (16 * NW), PER = APW + BPW;
-constexpr int STAGE = (BM + BN) * 64;
-__device__ __forceinline__ int swz(int r) { return (r & 1) ^ ((r >> 1) & 2); }
-__device__ __forceinline__ uint32_t roff(int row, int chunk) { return (uint32_t)(row * 64 + ((chunk ^ swz(row)) << 4)); }
+constexpr int STAGE = (BM + BN) * 64;   // 64-byte LDS rows at roff / swz (lds_dma.h)
 }  // namespace cg2
-
-template <int N>
-__device__ __forceinline__ void cg2_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
 
 // Epilogue of the v2 kernels for one wave's TM x TN 16 x 16 sub-tiles at
 // (row0, col0): plain fp32 / bf16 store, or the fused 2x2x2x2 max-pool.
@@ -359,8 +352,6 @@ template <bool OUT_BF16, bool POOL, int NS, bool F16 = false>
 __global__ __launch_bounds__(512, NS <= 3 ? 2 : 1) void corr_gemm_v2_kernel(GemmArgs p) {
   constexpr int BM = cg2::BM, BN = cg2::BN, BK = cg2::BK, GM = cg2::GM;
   constexpr int APW = cg2::APW, BPW = cg2::BPW, PER = cg2::PER, STAGE = cg2::STAGE;
-  using cg2::swz;
-  using cg2::roff;
   constexpr int TM = 4, TN = 4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -422,9 +413,9 @@ __global__ __launch_bounds__(512, NS <= 3 ? 2 : 1) void corr_gemm_v2_kernel(Gemm
   int buf = 0;
   for (int ks = 0; ks < nk; ++ks) {
     const int after = min(NS - 2, nk - 1 - ks);
-    if (after >= 2) cg2_wait_barrier<2 * PER>();
-    else if (after >= 1) cg2_wait_barrier<PER>();
-    else cg2_wait_barrier<0>();
+    if (after >= 2) dma_wait_barrier<2 * PER>();
+    else if (after >= 1) dma_wait_barrier<PER>();
+    else dma_wait_barrier<0>();
     if (ks + NS - 1 < nk) issue(ks + NS - 1, (buf + NS - 1) % NS);
     const char* As = smem + buf * STAGE;
     const char* Bs = As + BM * 64;
@@ -556,8 +547,8 @@ __global__ __launch_bounds__(512, 1) void corr_gemm_f8v2_kernel(GemmArgs p, int 
     for (int ks = 0; ks < nk; ++ks, ++g) {
       // stage g landed (the one after it may still be in flight; a previous
       // tile's epilogue stores, issued later, make this wait conservative)
-      if (g + 1 < nsteps) cg2_wait_barrier<PER>();
-      else cg2_wait_barrier<0>();
+      if (g + 1 < nsteps) dma_wait_barrier<PER>();
+      else dma_wait_barrier<0>();
       if (g + NS - 1 < nsteps) issue((buf + NS - 1) % NS);
       const char* As = smem + buf * STAGE;
       const char* Bs = As + BM * 128;

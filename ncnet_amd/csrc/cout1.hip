@@ -43,14 +43,6 @@ namespace ncnet {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void c1_static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    c1_static_for<B + 1, E>(f);
-  }
-}
-
 template <int KS, int K, int L, int RI, int RJ>
 struct CT1 {
   static constexpr int P = KS / 2, NT = KS * KS, NW = 4;
@@ -78,23 +70,6 @@ struct CT1 {
   static_assert(ZPAD >= P * L + P, "the gather's lowest tap offset stays inside the staging area");
 };
 
-// 16-B-per-lane buffer load into LDS (out-of-range offsets land as zeros),
-// issued from asm so the compiler's waitcnt pass never drains it.
-typedef int c1i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ c1i32x4 c1_rsrc(const void* base, uint32_t nbytes) {
-  const uint64_t b = (uint64_t)base;
-  c1i32x4 r;
-  r[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  r[1] = __builtin_amdgcn_readfirstlane((int)((uint32_t)(b >> 32) & 0xffffu));
-  r[2] = __builtin_amdgcn_readfirstlane((int)nbytes);
-  r[3] = 0x00020000;
-  return r;
-}
-__device__ __forceinline__ void c1_dma(const c1i32x4& rs, uint32_t voff, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "s"(lds)
-               : "memory", "m0");
-}
-
 // DBG (scripts/probe/cout1_probe.hip only): 1 no epilogue, 2 no DMA waits,
 // 4 no MFMAs -- timing decomposition, wrong results
 template <int KS, int K, int L, int RI, int RJ, int DBG = 0>
@@ -105,16 +80,16 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
   using C = CT1<KS, K, L, RI, RJ>;
   constexpr int P = C::P, NW = C::NW, MT = C::MT, NV = C::NV, WI = C::WI, WJ = C::WJ, NO = C::NO;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   // weights once per workgroup: NT KiB, wave w DMAs fragments w, w + 4, ...
   {
-    const c1i32x4 rs = c1_rsrc(Wt, C::NT * 1024);
-    for (int q = wave; q < C::NT; q += NW) c1_dma(rs, (uint32_t)((q * 64 + lane) * 16), lds0 + C::WOFF + q * 1024);
+    const i32x4 rs = make_rsrc(Wt, C::NT * 1024);
+    for (int q = wave; q < C::NT; q += NW) bdma16_lds(rs, (uint32_t)((q * 64 + lane) * 16), lds0 + C::WOFF + q * 1024);
   }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  dma_wait_barrier<0>();
 
   const int nbi = (I + RI - 1) / RI, nbj = (J + RJ - 1) / RJ;
   const int nitems = V * nbi * nbj;
@@ -153,10 +128,10 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
       const int ii = i0 - P + pi, jj = j0 - P + qj;
       const bool live = s < WI * WJ && ii >= 0 && ii < I && jj >= 0 && jj < J;
       const bf16* xp = xv + ((size_t)(live ? ii : 0) * J + (live ? jj : 0)) * plane_elems;
-      const c1i32x4 rs = c1_rsrc(xp, live ? (uint32_t)(NV * 32) : 0u);
+      const i32x4 rs = make_rsrc(xp, live ? (uint32_t)(NV * 32) : 0u);
       const uint32_t slot = ring + (uint32_t)((s % C::NSLOT) * C::SLOT);
 #pragma unroll
-      for (int m = 0; m < C::NDMA; ++m) c1_dma(rs, dvo[m], slot + m * 1024);
+      for (int m = 0; m < C::NDMA; ++m) bdma16_lds(rs, dvo[m], slot + m * 1024);
     };
     f32x16 acc[RI][RJ][MT];
 #pragma unroll
@@ -166,7 +141,7 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
 #pragma unroll
         for (int t = 0; t < MT; ++t) acc[a][b][t] = f32x16{};
     constexpr int NS = C::NSLOT, AHEAD = NS - 1;
-    c1_static_for<0, AHEAD>([&](auto qc) { issue(qc); });
+    static_for<0, AHEAD>([&](auto qc) { issue(qc); });
     // fragments of step s live in B[s & 1] / A[s & 1]; step s + 1's are read
     // while step s's MFMAs run (its plane landed: AHEAD - 1 steps of slack)
     bf16x8 B[2][MT], A[2][NO];
@@ -176,24 +151,24 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
 #pragma unroll
       for (int t = 0; t < MT; ++t)
         B[s & 1][t] = *(const bf16x8*)(smem + bbase + (uint32_t)((s % NS) * C::SLOT + t * 512));
-      c1_static_for<0, NO>([&](auto oc) {
+      static_for<0, NO>([&](auto oc) {
         constexpr int o = decltype(oc)::value, di = pi - o / RJ, dj = qj - o % RJ;
         if constexpr (di >= 0 && di < KS && dj >= 0 && dj < KS)
           A[s & 1][o] = *(const bf16x8*)(smem + abase + (uint32_t)((di * KS + dj) * 1024));
       });
     };
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * C::NDMA) : "memory");   // plane 0
+    dma_wait<(AHEAD - 1) * C::NDMA>();   // plane 0
     load_frags(std::integral_constant<int, 0>{});
-    c1_static_for<0, WI * WJ>([&](auto sc) {
+    static_for<0, WI * WJ>([&](auto sc) {
       constexpr int s = decltype(sc)::value;
       constexpr int pi = s / WJ, qj = s % WJ;
       issue(std::integral_constant<int, s + AHEAD>{});
       if constexpr (s + 1 < WI * WJ) {
         // this wave's slice of plane s + 1 has landed (s + 2 .. s + AHEAD may fly)
-        if constexpr (!(DBG & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((AHEAD - 1) * C::NDMA) : "memory");
+        if constexpr (!(DBG & 2)) dma_wait<(AHEAD - 1) * C::NDMA>();
         load_frags(std::integral_constant<int, s + 1>{});
       }
-      c1_static_for<0, NO>([&](auto oc) {
+      static_for<0, NO>([&](auto oc) {
         constexpr int o = decltype(oc)::value, a = o / RJ, b = o % RJ;
         constexpr int di = pi - a, dj = qj - b;
         if constexpr (di >= 0 && di < KS && dj >= 0 && dj < KS && !(DBG & 4)) {
@@ -204,7 +179,7 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
       });
     });
     // ---- epilogue: per output plane, Z_o -> LDS staging [tap][col], shift-sum
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");   // every ring read and DMA done
+    dma_wait_barrier<0>();   // every ring read and DMA done
     float* zs = (float*)(smem + C::ROFF) + C::ZPAD;
     // this thread's outputs o = tid + 256 m: per-tap validity as row / column
     // masks (1 / 0) and one staging base; tap (dk, dl) of output (k, l) reads
@@ -268,7 +243,7 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
     if constexpr (!(DBG & 1)) {
       write_z(std::integral_constant<int, 0>{});
       __syncthreads();
-      c1_static_for<0, NO>([&](auto oc) {
+      static_for<0, NO>([&](auto oc) {
         constexpr int o = decltype(oc)::value;
         const bool ok = o / RJ < na && o % RJ < nb;
         if constexpr (o + 1 < NO) {
@@ -279,7 +254,7 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
       });
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may land after the workgroup ends
+  dma_wait<0>();   // no LDS-DMA may land after the workgroup ends
 #endif
 }
 
