@@ -671,6 +671,56 @@ void score_sum(Tensor rmax, Tensor rse, Tensor cmax, Tensor cse, Tensor wr, Tens
                      (float*)out.data_ptr(), cur_stream(rmax)), "score_sum");
 }
 
+// keypoint-supervised loss (csrc/kploss.hip): x [B, R, C] with R = hA * wA, C = hB * wB; sp / tp [B, 2, N],
+// ssz / tsz [B, 3]; outputs cells int32 / wts fp32 [B, N, 8], valid int32 [B, N], lse / term [B, N, 2], out [2]
+void kploss_fwd(Tensor x, Tensor sp, Tensor tp, Tensor ssz, Tensor tsz, int64_t hA, int64_t wA, int64_t hB, int64_t wB,
+                Tensor cells, Tensor wts, Tensor valid, Tensor lse, Tensor term, Tensor out) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(x, "x", at::kFloat);
+  TORCH_CHECK(x.dim() == 3, "kploss_fwd: x must be [B, R, C]");
+  TORCH_CHECK(sp.dim() == 3, "kploss_fwd: source_points must be [B, 2, N]");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2), N = sp.size(2);
+  TORCH_CHECK(hA >= 1 && wA >= 1 && hB >= 1 && wB >= 1 && hA * wA == R && hB * wB == C,
+              "kploss_fwd: grid ", hA, "x", wA, " / ", hB, "x", wB, " does not match x ", x.sizes());
+  TORCH_CHECK(B >= 1 && N >= 1 && N <= 64, "kploss_fwd: 1 <= keypoints per image <= 64 (got ", N, ")");
+  TORCH_CHECK(B * N * 2 < (int64_t)1 << 31 && R < (int64_t)1 << 31 && C < (int64_t)1 << 31, "kploss_fwd: too large");
+  check(sp, "source_points", at::kFloat); check_shape(sp, "source_points", {B, 2, N});
+  check(tp, "target_points", at::kFloat); check_shape(tp, "target_points", {B, 2, N});
+  check(ssz, "source_im_size", at::kFloat); check_shape(ssz, "source_im_size", {B, 3});
+  check(tsz, "target_im_size", at::kFloat); check_shape(tsz, "target_im_size", {B, 3});
+  check(cells, "cells", at::kInt); check_shape(cells, "cells", {B, N, 8});
+  check(wts, "wts", at::kFloat); check_shape(wts, "wts", {B, N, 8});
+  check(valid, "valid", at::kInt); check_shape(valid, "valid", {B, N});
+  check(lse, "lse", at::kFloat); check_shape(lse, "lse", {B, N, 2});
+  check(term, "term", at::kFloat); check_shape(term, "term", {B, N, 2});
+  check(out, "out", at::kFloat); check_shape(out, "out", {2});
+  ok(ncnet_kploss_fwd((float*)x.data_ptr(), (float*)sp.data_ptr(), (float*)tp.data_ptr(), (float*)ssz.data_ptr(),
+                      (float*)tsz.data_ptr(), (int)B, (int)N, (int)hA, (int)wA, (int)hB, (int)wB,
+                      (int*)cells.data_ptr(), (float*)wts.data_ptr(), (int*)valid.data_ptr(), (float*)lse.data_ptr(),
+                      (float*)term.data_ptr(), (float*)out.data_ptr(), cur_stream(x)), "kploss_fwd");
+}
+
+// gx [B, R, C] = gscale * scale * dloss/dx (every element written); scale [1]: the forward's out[1:]
+void kploss_bwd(Tensor x, Tensor cells, Tensor wts, Tensor valid, Tensor lse, Tensor scale, Tensor gx,
+                c10::optional<Tensor> gscale) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(x, "x", at::kFloat); check(gx, "gx", at::kFloat);
+  TORCH_CHECK(x.dim() == 3 && gx.sizes() == x.sizes(), "kploss_bwd: x and gx must be [B, R, C]");
+  TORCH_CHECK(cells.dim() == 3, "kploss_bwd: cells must be [B, N, 8]");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2), N = cells.size(1);
+  TORCH_CHECK(B >= 1 && R >= 1 && C >= 1 && N >= 1 && N <= 64, "kploss_bwd: 1 <= keypoints per image <= 64 (got ", N, ")");
+  TORCH_CHECK(B * R < (int64_t)1 << 31 && C < (int64_t)1 << 31, "kploss_bwd: too large");
+  check(cells, "cells", at::kInt); check_shape(cells, "cells", {B, N, 8});
+  check(wts, "wts", at::kFloat); check_shape(wts, "wts", {B, N, 8});
+  check(valid, "valid", at::kInt); check_shape(valid, "valid", {B, N});
+  check(lse, "lse", at::kFloat); check_shape(lse, "lse", {B, N, 2});
+  check(scale, "scale", at::kFloat); TORCH_CHECK(scale.numel() == 1, "scale: one element");
+  if (gscale.has_value()) { check(*gscale, "gscale", at::kFloat); TORCH_CHECK(gscale->numel() == 1, "gscale: one element"); }
+  ok(ncnet_kploss_bwd((float*)x.data_ptr(), (int*)cells.data_ptr(), (float*)wts.data_ptr(), (int*)valid.data_ptr(),
+                      (float*)lse.data_ptr(), (float*)scale.data_ptr(), opt_ptr<float>(gscale), (float*)gx.data_ptr(),
+                      (int)B, (int)N, (int)R, (int)C, cur_stream(x)), "kploss_bwd");
+}
+
 void maxpool4d(Tensor x, Tensor y, Tensor code, int64_t ks) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16));
@@ -1152,6 +1202,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cmax"), py::arg("carg"), py::arg("cse"), py::arg("wr"), py::arg("wc"), py::arg("gx"), py::arg("norm"),
         py::arg("eps"), py::arg("gscale") = py::none());
   m.def("score_sum", &score_sum);
+  m.def("kploss_fwd", &kploss_fwd);
+  m.def("kploss_bwd", &kploss_bwd, py::arg("x"), py::arg("cells"), py::arg("wts"), py::arg("valid"), py::arg("lse"),
+        py::arg("scale"), py::arg("gx"), py::arg("gscale") = py::none());
   m.def("maxpool4d", &maxpool4d);
   m.def("transpose", &transpose);
   m.def("nc_fused_k3", &nc_fused_k3);

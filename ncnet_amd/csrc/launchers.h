@@ -218,6 +218,20 @@ int ncnet_maxpool4d(const void* x, int x_is_bf16, float* y, uint8_t* code, int V
 // x [V,R,C] -> y [V,C,R]; elem_bytes 2 or 4
 int ncnet_transpose(const void* x, void* y, int elem_bytes, int V, int R, int C, hipStream_t s);
 
+// ---- keypoint-supervised loss (csrc/kploss.hip) ---------------------------
+// x [B, R = hA*wA, C = hB*wB] fp32; sp / tp [B, 2, N] (x, y) 1-based pixels, -1 padded; ssz / tsz
+// [B, 3] (h, w, channels); 1 <= N <= 64 (else -3).  Writes the keypoint table (cells int32 [B, N, 8]
+// = four A cells then four B cells, wts fp32 [B, N, 8] likewise, valid int32 [B, N]), lse / term
+// [B, N, 2] (direction 0 A -> B, 1 B -> A; 0 for invalid keypoints) and out [2] =
+// (loss, 1 / (2 max(1, Nvalid))).
+int ncnet_kploss_fwd(const float* x, const float* sp, const float* tp, const float* ssz, const float* tsz, int B,
+                     int N, int hA, int wA, int hB, int wB, int* cells, float* wts, int* valid, float* lse,
+                     float* term, float* out, hipStream_t s);
+// gx [B, R, C] = gscale[0] (or 1: null) * scale[0] * dloss/dx from the forward's table and lse;
+// every element is written.
+int ncnet_kploss_bwd(const float* x, const int* cells, const float* wts, const int* valid, const float* lse,
+                     const float* scale, const float* gscale, float* gx, int B, int N, int R, int C, hipStream_t s);
+
 // ---- guarded flat Adam (csrc/optim.hip) -----------------------------------
 // g may be longer than p (trailing loss-indicator slot); count / skipped int32 [1], step fp32 [1].
 int ncnet_nonfinite_count(const float* g, long long n, int* count, hipStream_t s);

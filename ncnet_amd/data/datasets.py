@@ -207,6 +207,29 @@ class SyntheticPairDataset(Dataset):
         return {"source_image": a, "target_image": b, "source_im_size": size, "target_im_size": size, "set": 0}
 
 
+class SyntheticCorrespondenceDataset(Dataset):
+    """Synthetic pairs WITH keypoints (``train.py --loss strong --synthetic N``):
+    item ``i`` is ``synthetic_correspondence_batch(1, size, seed=seed * 100003 + i)``
+    without its batch axis, so it is deterministic per index.  Fields as
+    ``PFPascalDataset``: images [3, size, size], ``source_points`` /
+    ``target_points`` [2, n_points] (-1 padded), ``*_im_size`` [3], ``L_pck`` [1]."""
+
+    def __init__(self, length: int = 64, size: int = 400, seed: int = 0, n_points: int = 20):
+        self.length = length
+        self.size = int(size)
+        self.seed = seed
+        self.n_points = n_points
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, idx):
+        if not 0 <= idx < self.length:
+            raise IndexError(idx)
+        b = synthetic_correspondence_batch(1, self.size, seed=self.seed * 100003 + int(idx), n_points=self.n_points)
+        return {k: v[0].contiguous() for k, v in b.items()}
+
+
 def synthetic_batch(batch: int, image_size=(400, 400), device="cpu", seed: int = 0):
     """One batch of random normalised pairs generated directly on ``device``."""
     g = torch.Generator(device=device).manual_seed(seed)

@@ -1,4 +1,5 @@
-"""Weakly-supervised training loop (train.py:110-205), DP-aware.
+"""Weakly-supervised training loop (train.py:110-205), DP-aware; optionally
+keypoint-supervised (``Trainer(loss='strong')``, an extension beyond the reference).
 
 Differences from the reference, all semantics-preserving:
 * the negative pass reuses the positive-pass backbone features rolled by one
@@ -27,7 +28,7 @@ import torch
 
 from .. import config as _config
 
-from ..ops.loss import weak_loss_from_corr
+from ..ops.loss import strong_loss_from_corr, weak_loss_from_corr
 from ..parallel.dist import DistContext, GradBucket, all_reduce_mean
 from ..utils.timing import active as active_timer, segment
 
@@ -111,6 +112,42 @@ def weak_loss_from_features(model, feats, normalization: str | None = "softmax")
     return weak_loss_from_corr(model.weak_loss_volumes_from_features(f, hw, b), b, normalization)
 
 
+def strong_loss(model, batch) -> torch.Tensor:
+    """Keypoint-supervised loss (ops/reference.py keypoint_ce) of the positive
+    pairs: the model's volume against the batch's ``source_points`` /
+    ``target_points`` / ``*_im_size`` -- the fields eval/pck.py scores."""
+    return strong_loss_from_corr(_positive_volumes(model, batch), batch)
+
+
+def _positive_volumes(model, batch) -> torch.Tensor:
+    """The positive pairs' volumes [B,1,h,w,h,w] of a batch (backbone included)."""
+    src, tgt = batch["source_image"], batch["target_image"]
+    with segment("backbone"):
+        f, hw = model.extract(torch.cat((src, tgt), 0))
+    return model.match_volumes_from_features(f, hw, src.shape[0])
+
+
+def strong_loss_from_features(model, feats, batch) -> torch.Tensor:
+    """strong_loss on backbone features ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
+    f, hw, b = feats
+    return strong_loss_from_corr(model.match_volumes_from_features(f, hw, b), batch)
+
+
+_KEYPOINT_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size", "L_pck")
+
+
+def batch_pck(corr4d, batch, alpha: float = 0.1) -> torch.Tensor:
+    """Per-sample PCK@alpha [B] of a volume, by the evaluation's own path
+    (eval_pf_pascal.py: corr_to_matches with softmax, then pck_metric's
+    bilinear keypoint transfer); NaN for a sample without keypoints."""
+    from ..eval.pck import pck
+    from ..eval.point_tnf import PointsToPixelCoords, PointsToUnitCoords, bilinearInterpPointTnf, corr_to_matches
+    xA, yA, xB, yB, _ = corr_to_matches(corr4d.float(), do_softmax=True)
+    tp_norm = PointsToUnitCoords(batch["target_points"], batch["target_im_size"])
+    warped = PointsToPixelCoords(bilinearInterpPointTnf((xA, yA, xB, yB), tp_norm), batch["source_im_size"])
+    return pck(batch["source_points"], warped, batch["L_pck"].view(-1).to(warped.dtype), alpha)
+
+
 class TrunkPrefetcher:
     """Software pipeline over training steps: the frozen backbone (+ L2-norm
     packing) of batch t+1 runs on a side HIP stream while step t's
@@ -177,8 +214,18 @@ class TrunkPrefetcher:
 
 
 class Trainer:
+    """``loss``: ``'weak'`` (the reference's objective, the default) or
+    ``'strong'`` -- the keypoint-supervised loss on batches that carry
+    ``source_points`` / ``target_points`` / ``*_im_size``.  Under data
+    parallelism each rank normalises the strong loss by its OWN number of valid
+    keypoints and the gradients are then averaged over ranks as for the weak
+    loss (so ranks, not keypoints, weigh equally)."""
+
     def __init__(self, model, optimizer, ctx: DistContext, normalization="softmax", nan_guard=True,
-                 metrics_path: str | None = None, fault_step: int | None = None):
+                 metrics_path: str | None = None, fault_step: int | None = None, loss: str = "weak"):
+        if loss not in ("weak", "strong"):
+            raise ValueError(f"loss must be 'weak' or 'strong', got {loss!r}")
+        self.loss = loss
         self.model = model
         self.opt = optimizer
         self.ctx = ctx
@@ -198,6 +245,8 @@ class Trainer:
         self.fault_step = fault_step if fault_step is not None else _config.RUNTIME.fault_step
         self.prefetch = TrunkPrefetcher(model)
         self.batch_to_device = None       # optional hook: host batch -> device batch (train.py: GPU resize)
+        self._pck = []                    # per-sample PCK of the evaluation steps (loss='strong')
+        self.last_pck = None              # PCK@0.1 of the last evaluation epoch (loss='strong')
 
     def _move(self, batch):
         if self.batch_to_device is not None:
@@ -228,7 +277,19 @@ class Trainer:
         with segment("forward"):
             feats = self.prefetch.take(batch)
             self.prefetch.submit(next_batch)
-            loss = weak_loss_from_features(self.model, feats, self.normalization)
+            if self.loss == "strong":
+                if self.prefetch.enabled:
+                    # the keypoint tensors were moved on the prefetch stream with the images
+                    # (to_device); take() made the main stream wait for it, and like the
+                    # features they must not be recycled there while this step reads them
+                    main = torch.cuda.current_stream(self.prefetch.stream.device)
+                    for k in _KEYPOINT_FIELDS:
+                        v = batch.get(k)
+                        if torch.is_tensor(v) and v.is_cuda:
+                            v.record_stream(main)
+                loss = strong_loss_from_features(self.model, feats, batch)
+            else:
+                loss = weak_loss_from_features(self.model, feats, self.normalization)
         with segment("backward"):
             loss.backward()
         if self.flat and self.nan_guard:
@@ -270,6 +331,11 @@ class Trainer:
             for v in batch.values():
                 if torch.is_tensor(v) and v.is_cuda:
                     v.record_stream(main)
+        if self.loss == "strong":
+            vol = _positive_volumes(self.model, batch)
+            if "L_pck" in batch:              # PCK of the same volume, summarised per epoch by process_epoch
+                self._pck.append(batch_pck(vol, batch))
+            return strong_loss_from_corr(vol, batch).detach()
         return weak_loss(self.model, batch, self.normalization).detach()
 
     def _log(self, rec: dict):
@@ -292,6 +358,7 @@ class Trainer:
         nxt = self.to_device(nxt) if nxt is not None else None
         batch_idx = -1
         log = AsyncLossLog(self.ctx.device, sync=sync_log)
+        self._pck = []
 
         def emit(recs):
             for rec in recs:
@@ -325,4 +392,12 @@ class Trainer:
         mean = float(all_reduce_mean(total / max(n, 1), self.ctx))
         if self.ctx.is_main:
             print(f"{mode.capitalize()} set: Average loss: {mean:.4f}", flush=True)
+        if not is_train and self.loss == "strong" and self._pck:
+            # mean over this rank's samples with keypoints, then over ranks
+            pck = torch.cat(self._pck).float()
+            self._pck = []
+            self.last_pck = float(all_reduce_mean(torch.nanmean(pck), self.ctx))
+            if self.ctx.is_main:
+                print(f"{mode.capitalize()} set: PCK@0.1: {self.last_pck:.4f}", flush=True)
+            self._log({"mode": mode, "epoch": epoch, "pck": self.last_pck})
         return mean

@@ -415,6 +415,20 @@ class ImMatchNet(nn.Module):
             return corr4d, delta
         return corr4d
 
+    def match_volumes_from_features(self, f: torch.Tensor, hw, b: int) -> torch.Tensor:
+        """The positive volumes [B,1,h,w,h,w] alone, from ``f`` = extract() of
+        the 2B images [source; target] (the keypoint-supervised loss: no rolled
+        negatives, so the NC stack runs on half the volumes of a weak step)."""
+        h, w = hw
+        with segment("correlation"):
+            if isinstance(f, tuple):           # split operands (nc_precision / corr_dtype 'fp32')
+                if _nc_ops.x3_dropped("corr"):
+                    f = (f[0], torch.zeros_like(f[1]))
+                corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]))
+            else:
+                corr = correlation(f[:b], f[b:])
+        return self.process_correlation(corr.view(b, 1, h, w, h, w))
+
     def weak_loss_volumes(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
         """Positive and rolled-negative volumes [2B,1,h,w,h,w] for the weak loss.
 

@@ -10,6 +10,10 @@ closed-form backward kernel:
   the volumes are non-negative -- ReLU'd NC outputs after MutualMatching -- so
   the positive denominator keeps the argmax), ``ds/dx_j = delta_{j, argmax} / D - max / D^2``;
 * ``None``: ``max x``, ``ds/dx_j = delta_{j, argmax}``.
+
+``strong_loss_from_corr`` is the keypoint-supervised objective (an extension
+beyond the reference; ``reference.keypoint_ce``) on the fused forward /
+closed-form backward kernels of csrc/kploss.hip.
 """
 from __future__ import annotations
 
@@ -104,6 +108,61 @@ def weak_loss_from_corr(corr4d: torch.Tensor, n_pos: int, normalization: str | N
     pos = ref.match_score(corr4d[:b], normalization)
     neg = ref.match_score(corr4d[b:], normalization)
     return neg - pos
+
+
+class KeypointCEFn(torch.autograd.Function):
+    """ops/reference.py keypoint_ce on the HIP kernels of csrc/kploss.hip: the
+    forward builds the keypoint table on the device and saves it with the
+    log-sum-exps; the backward is the closed form, scaled by the incoming
+    gradient and 1 / (2 Nvalid) inside the kernel (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, x3, sp, tp, ssz, tsz, grid):
+        x3 = x3.float().contiguous()
+        B, N = x3.shape[0], sp.shape[2]
+        dev = x3.device
+        cells = torch.empty((B, N, 8), dtype=torch.int32, device=dev)
+        wts = torch.empty((B, N, 8), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, N), dtype=torch.int32, device=dev)
+        lse = torch.empty((B, N, 2), dtype=torch.float32, device=dev)
+        term = torch.empty((B, N, 2), dtype=torch.float32, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _ext.ext().kploss_fwd(x3, sp, tp, ssz, tsz, *grid, cells, wts, valid, lse, term, out)
+        ctx.save_for_backward(x3, cells, wts, valid, lse, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x3, cells, wts, valid, lse, out = ctx.saved_tensors
+        gx = torch.empty_like(x3)
+        _ext.ext().kploss_bwd(x3, cells, wts, valid, lse, out[1:], gx, g.float().contiguous().reshape(1))
+        return gx, None, None, None, None, None
+
+
+_KP_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size")
+
+
+def strong_loss_from_corr(corr4d: torch.Tensor, batch) -> torch.Tensor:
+    """Keypoint-supervised loss (ops/reference.py keypoint_ce) of a
+    [B,1,hA,wA,hB,wB] volume against the batch's ``source_points`` /
+    ``target_points`` [B,2,N] and ``*_im_size`` [B,3].  The keypoint tensors are
+    used as they are when they already are contiguous fp32 on the volume's
+    device (the trainer moves the batch once); nothing is copied per step."""
+    missing = [k for k in _KP_FIELDS if k not in batch]
+    if missing:
+        raise KeyError(f"strong loss: the batch has no {missing} (use a dataset with keypoints)")
+    if corr4d.dim() != 6 or corr4d.shape[1] != 1:
+        raise ValueError(f"strong loss: expected a [B,1,hA,wA,hB,wB] volume, got {tuple(corr4d.shape)}")
+    sp, tp, ssz, tsz = (batch[k] for k in _KP_FIELDS)
+    if _ext.use_hip(corr4d):
+        b = corr4d.shape[0]
+        ha, wa, hb, wb = corr4d.shape[2:]
+        if sp.shape[2] > 64:
+            raise ValueError(f"strong loss: at most 64 keypoints per image on the GPU (got {sp.shape[2]})")
+        sp, tp, ssz, tsz = (t.to(device=corr4d.device, dtype=torch.float32).contiguous() for t in (sp, tp, ssz, tsz))
+        _ext.count("kploss")
+        return KeypointCEFn.apply(corr4d.reshape(b, ha * wa, hb * wb), sp, tp, ssz, tsz, (ha, wa, hb, wb))
+    return ref.keypoint_ce(corr4d, sp, tp, ssz, tsz)
 
 
 def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> torch.Tensor:

@@ -19,6 +19,8 @@ depends on torch-0.3 semantics:
                              lib/conv4d.py:39-48), kept only as the measured
                              baseline for bench.py
 * ``softmax_max_scores``  -- the weak-loss scores of train.py:121-134
+* ``keypoint_ce``         -- the keypoint-supervised loss (an extension; no
+                             counterpart in the reference)
 
 Weight layout: Conv4d weights are stored the way the reference checkpoints
 store them, pre-permuted to ``[k, out, in, k, k, k]`` (lib/conv4d.py:75-77).
@@ -189,6 +191,79 @@ def softmax_max_scores(corr4d: torch.Tensor, normalization: str | None = "softma
     scores_b = norm(mat, 1).max(dim=1)[0]  # per B cell, over A
     scores_a = norm(mat, 2).max(dim=2)[0]  # per A cell, over B
     return scores_a, scores_b
+
+
+def _keypoint_axis(p: torch.Tensor, size: torch.Tensor, n: int):
+    """Cells i0, i1 and fraction f of the 1-based pixel coordinates ``p`` [B, N]
+    on an n-cell axis of images ``size`` [B] pixels long -- the mapping the PCK
+    evaluation uses (eval/point_tnf.py normalize_axis)."""
+    from ..eval.point_tnf import normalize_axis
+    u = ((normalize_axis(p, size.unsqueeze(1)) + 1) / 2 * (n - 1)).clamp(0, n - 1)
+    i0 = u.floor().clamp(max=max(n - 2, 0)).long()
+    i1 = (i0 + 1).clamp(max=n - 1)
+    return i0, i1, u - i0.to(u.dtype)
+
+
+def keypoint_weight_maps(points: torch.Tensor, im_size: torch.Tensor, h: int, w: int, dtype=None) -> torch.Tensor:
+    """[B, 2, N] (x, y) keypoints -> dense bilinear weight maps [B, N, h*w]: four
+    cells per keypoint with weights (1-fi)(1-fj), (1-fi)fj, fi(1-fj), fi*fj
+    (i: the y / row axis, j: the x / column axis); cells that coincide add up."""
+    dtype = dtype or points.dtype
+    p, sz = points.to(dtype), im_size.to(dtype)
+    i0, i1, fi = _keypoint_axis(p[:, 1], sz[:, 0], h)
+    j0, j1, fj = _keypoint_axis(p[:, 0], sz[:, 1], w)
+    out = torch.zeros(p.shape[0], p.shape[2], h * w, dtype=dtype, device=p.device)
+    for ci, wi in ((i0, 1 - fi), (i1, fi)):
+        for cj, wj in ((j0, 1 - fj), (j1, fj)):
+            out.scatter_add_(2, (ci * w + cj).unsqueeze(2), (wi * wj).unsqueeze(2))
+    return out
+
+
+def keypoint_valid(source_points: torch.Tensor, target_points: torch.Tensor) -> torch.Tensor:
+    """[B, N] bool: all four coordinates of the pair differ from the -1 padding."""
+    return ((source_points != -1).all(1)) & ((target_points != -1).all(1))
+
+
+def _keypoint_maps(corr4d, source_points, target_points, source_im_size, target_im_size):
+    b, _, ha, wa, hb, wb = corr4d.shape
+    dt, dev = corr4d.dtype, corr4d.device
+    sp, tp = source_points.to(dev), target_points.to(dev)
+    valid = keypoint_valid(sp, tp).to(dt).unsqueeze(2)
+    U = keypoint_weight_maps(sp, source_im_size.to(dev), ha, wa, dt) * valid      # [B, N, R]
+    V = keypoint_weight_maps(tp, target_im_size.to(dev), hb, wb, dt) * valid      # [B, N, C]
+    return corr4d.reshape(b, ha * wa, hb * wb), U, V, valid
+
+
+def keypoint_ce(corr4d: torch.Tensor, source_points: torch.Tensor, target_points: torch.Tensor,
+                source_im_size: torch.Tensor, target_im_size: torch.Tensor) -> torch.Tensor:
+    """Keypoint-supervised cross-entropy on a [B,1,hA,wA,hB,wB] volume (an
+    extension beyond the reference; the contract of csrc/kploss.hip).
+
+    Points are [B, 2, N] (x, y) in 1-based pixels of the original images, -1
+    padded; sizes [B, 3] (h, w, channels) -- the fields eval/pck.py consumes.
+    With U_n / V_n the bilinear weight maps of keypoint n on the A / B grid and
+    x = corr4d.view(B, R, C):
+        s_n = U_n . x (a blend of four rows),      L_ab = -sum_m V_n(m) log_softmax(s_n)[m]
+        t_n = x . V_n (a blend of four columns),   L_ba = -sum_r U_n(r) log_softmax(t_n)[r]
+        loss = sum over valid keypoints of (L_ab + L_ba) / (2 max(1, Nvalid))
+    A batch without a valid keypoint gives 0 (and a zero gradient)."""
+    x, U, V, valid = _keypoint_maps(corr4d, source_points, target_points, source_im_size, target_im_size)
+    s = torch.einsum("bnr,brc->bnc", U, x)
+    t = torch.einsum("bnc,brc->bnr", V, x)
+    l_ab = -(V * torch.log_softmax(s, dim=2)).sum(2)
+    l_ba = -(U * torch.log_softmax(t, dim=2)).sum(2)
+    return (l_ab + l_ba).sum() / (2 * valid.sum().clamp(min=1))
+
+
+def keypoint_ce_grad(corr4d: torch.Tensor, source_points: torch.Tensor, target_points: torch.Tensor,
+                     source_im_size: torch.Tensor, target_im_size: torch.Tensor) -> torch.Tensor:
+    """Closed-form d keypoint_ce / d corr4d (what the HIP backward evaluates):
+    1 / (2 Nvalid) sum_n [U_n(r) (softmax(s_n)[m] - V_n(m)) + (softmax(t_n)[r] - U_n(r)) V_n(m)]."""
+    x, U, V, valid = _keypoint_maps(corr4d, source_points, target_points, source_im_size, target_im_size)
+    ps = torch.softmax(torch.einsum("bnr,brc->bnc", U, x), dim=2) * valid
+    pt = torch.softmax(torch.einsum("bnc,brc->bnr", V, x), dim=2) * valid
+    g = torch.einsum("bnr,bnc->brc", U, ps - V) + torch.einsum("bnr,bnc->brc", pt - U, V)
+    return (g / (2 * valid.sum().clamp(min=1))).reshape(corr4d.shape)
 
 
 def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> torch.Tensor:

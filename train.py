@@ -9,6 +9,12 @@ Same flags and defaults as the reference, plus:
   --sync_log           synchronous per-step loss readback, as the reference
   --resume PATH        real resume: weights + optimizer + epoch + RNG state
   --max_steps S        stop after S training steps (smoke / profiling)
+  --loss weak|strong   weak (default): the reference's objective.  strong: the
+                       keypoint-supervised cross-entropy (ops/reference.py
+                       keypoint_ce) on pairs with annotated correspondences:
+                       --synthetic N (synthetic pairs with known keypoints) or
+                       --train_pairs_csv / --val_pairs_csv (test_pairs.csv
+                       layout); every validation epoch also reports PCK@0.1
   --metrics PATH       JSONL metrics (rank 0)
   --dtype bf16|fp32    backbone compute dtype of the default (bf16) NC mode
   --nc_precision bf16|mixed|fp32
@@ -49,7 +55,8 @@ from torch.utils.data import DataLoader, Subset
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from ncnet_amd.data import ImagePairDataset, NormalizeImageDict, SyntheticPairDataset  # noqa: E402
+from ncnet_amd.data import (ImagePairDataset, NormalizeImageDict, PFPascalDataset,  # noqa: E402
+                            SyntheticCorrespondenceDataset, SyntheticPairDataset)
 from ncnet_amd.data.datasets import collate_uint8_pairs, gpu_pair_batch  # noqa: E402
 from ncnet_amd.engine.checkpoint import capture_rng, load_checkpoint, restore_rng, save_checkpoint  # noqa: E402
 from ncnet_amd.engine.trainer import AsyncLossLog, Trainer, make_adam  # noqa: E402
@@ -93,6 +100,13 @@ def build_parser():
                         "and backward (fp32-class forward numerics at ~1/3 less NC cost than fp32). Over 24 seeds "
                         "bf16, mixed and fp32 took off at the same rate (profiles/r5/ablation): there is no evidence "
                         "that either learns where bf16 does not; pick them for forward numerics, not for learning")
+    p.add_argument("--loss", type=str, default="weak", choices=["weak", "strong"],
+                   help="weak: the reference's weakly-supervised score; strong: keypoint-supervised cross-entropy "
+                        "on pairs with annotated correspondences (--synthetic N, or --train_pairs_csv / "
+                        "--val_pairs_csv in the test_pairs.csv layout)")
+    p.add_argument("--train_pairs_csv", type=str, default="",
+                   help="--loss strong: training pairs with keypoints (source,target,class,XA,YA,XB,YB)")
+    p.add_argument("--val_pairs_csv", type=str, default="", help="--loss strong: validation pairs with keypoints")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--segment_timing", action="store_true")
     p.add_argument("--profile", type=str, default="")
@@ -117,6 +131,11 @@ class _Shard(torch.utils.data.Sampler):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    strong = args.loss == "strong"
+    if strong and not args.synthetic and not (args.train_pairs_csv and args.val_pairs_csv):
+        raise SystemExit("--loss strong needs pairs with keypoints: give --synthetic N, or --train_pairs_csv and "
+                         "--val_pairs_csv (test_pairs.csv layout: source,target,class,XA,YA,XB,YB); "
+                         "the shipped train_pairs.csv / val_pairs.csv carry no keypoints")
     ctx = init_distributed()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -147,7 +166,19 @@ def main(argv=None):
 
     size = (args.image_size, args.image_size)
     gpu_resize = ctx.device.type == "cuda" and not args.cpu_resize
-    if args.synthetic:
+    if strong:
+        # keypoint datasets yield float images (no uint8 GPU-resize path)
+        gpu_resize = False
+        if args.synthetic:
+            train_set = SyntheticCorrespondenceDataset(args.synthetic, args.image_size, seed=1)
+            test_set = SyntheticCorrespondenceDataset(max(2 * args.batch_size, args.synthetic // 8), args.image_size,
+                                                      seed=2)
+        else:
+            norm = NormalizeImageDict(["source_image", "target_image"])
+            train_set = PFPascalDataset(args.train_pairs_csv, args.dataset_image_path, output_size=size,
+                                        transform=norm)
+            test_set = PFPascalDataset(args.val_pairs_csv, args.dataset_image_path, output_size=size, transform=norm)
+    elif args.synthetic:
         train_set = SyntheticPairDataset(args.synthetic, size, seed=1)
         test_set = SyntheticPairDataset(max(2 * args.batch_size, args.synthetic // 8), size, seed=2)
     else:
@@ -196,7 +227,7 @@ def main(argv=None):
 
     timer = SegmentTimer(device=ctx.device) if args.segment_timing else None
     set_active(timer)
-    trainer = Trainer(model, optimizer, ctx, metrics_path=args.metrics or None)
+    trainer = Trainer(model, optimizer, ctx, metrics_path=args.metrics or None, loss=args.loss)
     trainer.batch_to_device = trainer_to_device
     if args.max_steps:
         # bounded run (smoke / profiling)
