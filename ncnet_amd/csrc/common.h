@@ -128,6 +128,9 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblocks) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// whether 16-byte (float4) loads may start at p: a contiguous view into a larger
+// buffer can begin at any element, so launchers test this next to the row length
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // ---- staged (k, l) plane geometry of the Conv4d kernels (fwd and wgrad) ----
 // Element offset of plane (v, i, j) of a channels-last [V, I, J, K, L, C]

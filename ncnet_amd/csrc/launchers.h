@@ -185,6 +185,7 @@ int ncnet_stats_cols(const float* x, float* mx, int* arg, float* se, int V, int 
                      int sum_kind, hipStream_t s);
 // row and column stats in one pass: work = 3 * V * (nct * R + nrt * C) floats of partials
 // (nrt = ceil(R / 64), nct = ceil(C / 256)).  sum_kind 0: max / argmax only (rse, cse ignored).
+// 16-byte loads when C % 4 == 0 and x is 16-byte aligned, else scalar loads (any alignment).
 int ncnet_stats2d(const float* x, float* rmx, int* rarg, float* rse, float* cmx, int* carg, float* cse, int V, int R,
                   int C, float* work, int sum_kind, hipStream_t s);
 // one volume's bidirectional match candidates from its column (B cells) and row (A cells)
@@ -197,7 +198,8 @@ int ncnet_match_candidates(const float* cmx, const float* cse, const int* carg, 
 int ncnet_mm_apply(const float* c, const float* rmax, const float* cmax, float* out_f32, void* out_x, void* out_xt,
                    int V, int R, int C, float eps, int x_f16, int pad_ks, int I2, int J2, int K2, int L2,
                    hipStream_t s);
-// work: nullptr (separate row / column passes) or V * (ceil(C/256) * R + ceil(R/64) * C) floats (one pass)
+// work: nullptr (separate row / column passes) or V * (ceil(C/256) * R + ceil(R/64) * C) floats (one pass;
+// 16-byte loads when C % 4 == 0 and c, g are 16-byte aligned, else scalar loads)
 int ncnet_mm_bwd(const float* c, const float* g, const float* rmax, const int* rarg, const float* cmax,
                  const int* carg, float* rsum, float* csum, float* gc, int V, int R, int C, float eps, float* work,
                  hipStream_t s);

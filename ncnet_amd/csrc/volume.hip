@@ -754,7 +754,8 @@ extern "C" int ncnet_stats_cols(const float* x, float* mx, int* arg, float* se, 
 }
 extern "C" int ncnet_stats2d(const float* x, float* rmx, int* rarg, float* rse, float* cmx, int* carg, float* cse,
                              int V, int R, int C, float* work, int sum_kind, hipStream_t s) {
-  const bool vec = C % 4 == 0;   // 16-byte rows: one float4 per lane and row; else four scalar loads
+  // 16-byte rows from a 16-byte aligned base: one float4 per lane and row; else four scalar loads
+  const bool vec = C % 4 == 0 && aligned16(x);
   // tall volumes: 64 rt-row blocks (rt x fewer column partials to merge;
   // tuning s2d_rt); the work buffer is sized for 64-row blocks (the bound)
   const int rt = R >= 1024 ? (tuning().s2d_rt >= 4 ? 4 : tuning().s2d_rt == 2 ? 2 : 1) : 1;
@@ -813,7 +814,7 @@ extern "C" int ncnet_mm_bwd(const float* c, const float* g, const float* rmax, c
     float* rp = work;
     float* cp = work + (size_t)V * nct * R;
     const dim3 grid((unsigned)((size_t)V * nrt * nct));
-    dispatch_bool(C % 4 == 0, [&](auto vc) {   // 16-byte rows: vector loads
+    dispatch_bool(C % 4 == 0 && aligned16(c) && aligned16(g), [&](auto vc) {   // 16-byte aligned rows: vector loads
       hipLaunchKernelGGL((mm_bwd_sums2d_kernel<decltype(vc)::value>), grid, dim3(256), 0, s, c, g, rmax, cmax, R, C, nrt,
                          nct, rp, cp, eps);
     });

@@ -45,7 +45,8 @@ def _best(mat: torch.Tensor, dim: int, do_softmax: bool):
 def best_both(corr4d, do_softmax: bool):
     """The (score, index) of the best entry along both directions of the
     volume in one pass (stats2d) -> ((score_B, idx_B), (score_A, idx_A)), or
-    None where stats2d does not apply (CPU, or rows not a 16-byte multiple)."""
+    None where stats2d does not apply (CPU, or a volume that is not fp32);
+    any row length and alignment (scalar loads where 16-byte ones cannot be used)."""
     b, _, fs1, fs2, fs3, fs4 = corr4d.shape
     mat = corr4d.reshape(b, fs1 * fs2, fs3 * fs4)
     if not (_ext.use_hip(mat) and mat.dtype == torch.float32):

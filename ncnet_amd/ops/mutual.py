@@ -27,7 +27,7 @@ def _stats(c3: torch.Tensor):
     rarg = torch.empty((V, R), dtype=torch.int32, device=c3.device)
     cmax = torch.empty((V, Cc), dtype=torch.float32, device=c3.device)
     carg = torch.empty((V, Cc), dtype=torch.int32, device=c3.device)
-    # both maxima in one pass over the volume (stats2d) when rows are 16-byte multiples
+    # both maxima in one pass over the volume (stats2d: any row length and alignment)
     if not (_config.RUNTIME.stats2d and C.stats2d(c3, rmax, rarg, None, cmax, carg, None, 0)):
         C.stats_rows(c3, rmax, rarg, None, 0)
         C.stats_cols(c3, cmax, carg, None, 0)
