@@ -1031,6 +1031,29 @@ void resize_norm_u8(Tensor src, Tensor meta, Tensor out, std::vector<double> mea
      "resize_norm_u8");
 }
 
+// The augmenting variant (csrc/dataprep.hip warp_norm_u8_kernel): as resize_norm_u8, plus params fp32 [B, 8] =
+// (a0..a5, gain, bias) per image on the same device.  Any parameter values are safe: the kernel clamps the
+// sampling position into the image.
+void warp_norm_u8(Tensor src, Tensor meta, Tensor params, Tensor out, std::vector<double> mean,
+                  std::vector<double> stdv) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
+  check(src, "src", at::kByte); check(meta, "meta", at::kLong); check(params, "params", at::kFloat);
+  check(out, "out", at::kFloat);
+  TORCH_CHECK(src.dim() == 1, "src must be a flat byte buffer");
+  TORCH_CHECK(meta.dim() == 2 && meta.size(1) == 3, "meta must be [B, 3]");
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == meta.size(0) && params.size(1) == 8, "params must be [B, 8]");
+  TORCH_CHECK(meta.device() == src.device() && params.device() == src.device() && out.device() == src.device(),
+              "src, meta, params and out must be on one device");
+  TORCH_CHECK(out.dim() == 4 && out.size(0) == meta.size(0) && out.size(1) == 3, "out must be [B, 3, oh, ow]");
+  TORCH_CHECK(mean.size() == 3 && stdv.size() == 3, "mean / std need 3 values");
+  const float m[3] = {(float)mean[0], (float)mean[1], (float)mean[2]};
+  const float sd[3] = {(float)stdv[0], (float)stdv[1], (float)stdv[2]};
+  ok(ncnet_warp_norm_u8(src.data_ptr(), (const long long*)meta.data_ptr(), (const float*)params.data_ptr(),
+                        (float*)out.data_ptr(), (int)out.size(0), (int)out.size(2), (int)out.size(3), m, sd,
+                        cur_stream(src)),
+     "warp_norm_u8");
+}
+
 // Minimal P3P solver (csrc/pnp.hip), test entry point: rays / X [M, 3, 3] fp64
 // (row k = k-th bearing vector / world point) -> (P [M, 4, 3, 4] with the valid
 // poses first and NaN after them, nsol [M] int32).
@@ -1210,6 +1233,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nc_fused_k3", &nc_fused_k3);
   m.def("nc_fused_k3_f8", &nc_fused_k3_f8);
   m.def("resize_norm_u8", &resize_norm_u8);
+  m.def("warp_norm_u8", &warp_norm_u8);
   m.def("debug_selftest", &debug_selftest);
   m.def("p3p_solve", &p3p_solve);
   m.def("p3p_ransac_batch", &p3p_ransac_batch, py::arg("rays"), py::arg("X"), py::arg("offsets"), py::arg("keys"),

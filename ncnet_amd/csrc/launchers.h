@@ -246,6 +246,9 @@ int ncnet_adam_finalize(float* step, int* count, int* skipped, hipStream_t s);
 // (byte offset, H, W) (device), out fp32 [B, 3, oh, ow]; mean / stdv: 3 host floats each.
 int ncnet_resize_norm_u8(const void* src, const long long* meta, float* out, int B, int oh, int ow, const float* mean,
                          const float* stdv, hipStream_t stream);
+// The same with a per-image affine sampling map and gain / bias: params fp32 [B, 8] = (a0..a5, gain, bias) (device).
+int ncnet_warp_norm_u8(const void* src, const long long* meta, const float* params, float* out, int B, int oh, int ow,
+                       const float* mean, const float* stdv, hipStream_t stream);
 
 // ---- P3P LO-RANSAC (csrc/pnp.hip) -----------------------------------------
 // rays / X [M, 3, 3] fp64 -> P [M, 4, 3, 4] (valid poses first, NaN after), nsol [M]

@@ -1,6 +1,7 @@
+from .augment import PairAugment
 from .datasets import (ImagePairDataset, PFPascalDataset, SyntheticCorrespondenceDataset, SyntheticPairDataset,
                        synthetic_batch)
 from .transforms import AffineTnf, NormalizeImageDict, normalize_image, resize_bilinear
 
-__all__ = ["ImagePairDataset", "PFPascalDataset", "SyntheticCorrespondenceDataset", "SyntheticPairDataset",
+__all__ = ["PairAugment", "ImagePairDataset", "PFPascalDataset", "SyntheticCorrespondenceDataset", "SyntheticPairDataset",
            "synthetic_batch", "AffineTnf", "NormalizeImageDict", "normalize_image", "resize_bilinear"]

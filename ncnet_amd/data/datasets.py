@@ -92,13 +92,22 @@ def collate_uint8_pairs(samples):
     return out
 
 
-def gpu_pair_batch(batch, device, out_h: int, out_w: int):
+def gpu_pair_batch(batch, device, out_h: int, out_w: int, augment=None, generator=None):
     """Move a ``collate_uint8_pairs`` batch to ``device`` (uint8 pixels: 4x
     fewer bytes than float, one non-blocking copy) and resize + normalise all
     images there in one HIP launch (csrc/dataprep.hip): bilinear with
     align_corners=True as the reference's identity AffineTnf
     (lib/transformation.py), then ImageNet normalisation
-    (lib/normalization.py).  On CPU the same math runs through torch."""
+    (lib/normalization.py).  On CPU the same math runs through torch.
+
+    ``augment`` (a ``data.augment.PairAugment``, with a CPU ``generator``): the
+    launch is ``warp_norm_u8`` instead, which also warps and jitters every
+    image by a row of parameters drawn here on the host (``draw_params``) and
+    uploaded next to ``pixel_meta``.  If the batch carries keypoints they are
+    moved through the same maps on the host first: ``source_points`` /
+    ``target_points`` are rewritten in the output frame (index k of BOTH sets
+    becomes -1 when either point leaves its frame), ``source_im_size`` /
+    ``target_im_size`` become ``(out_h, out_w, 3)``; ``L_pck`` stays."""
     from .transforms import IMAGENET_MEAN, IMAGENET_STD, gpu_normalize_resize
     from ..ops import _ext
     pix, meta = batch["pixels"], batch["pixel_meta"]
@@ -106,14 +115,29 @@ def gpu_pair_batch(batch, device, out_h: int, out_w: int):
     ends = meta[:, 0] + meta[:, 1] * meta[:, 2] * 3
     if int(ends.max()) > pix.numel() or int(meta[:, 1:].min()) < 1:
         raise ValueError("malformed pixel table")
+    params = None
+    if augment is not None:
+        from .augment import draw_params, transform_pair_points
+        params = draw_params(meta, out_h, out_w, augment, generator)
+        if "source_points" in batch:
+            sp, tp = transform_pair_points(batch["source_points"], batch["target_points"], params, out_h, out_w)
+            size = torch.tensor([float(out_h), float(out_w), 3.0]).expand(n // 2, 3).contiguous()
+            batch = dict(batch, source_points=sp, target_points=tp, source_im_size=size, target_im_size=size.clone())
     res = {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch.items()
            if k not in ("pixels", "pixel_meta")}
     dev = torch.device(device)
     pix_d = pix.to(dev, non_blocking=True) if dev.type == "cuda" else None   # the batch's ONE pixel copy
     if pix_d is not None and _ext.use_hip(pix_d):
         out = torch.empty((n, 3, out_h, out_w), dtype=torch.float32, device=dev)
-        _ext.ext().resize_norm_u8(pix_d, meta.to(dev, non_blocking=True), out, list(IMAGENET_MEAN),
-                                  list(IMAGENET_STD))
+        if params is None:
+            _ext.ext().resize_norm_u8(pix_d, meta.to(dev, non_blocking=True), out, list(IMAGENET_MEAN),
+                                      list(IMAGENET_STD))
+        else:
+            _ext.ext().warp_norm_u8(pix_d, meta.to(dev, non_blocking=True), params.to(dev, non_blocking=True), out,
+                                    list(IMAGENET_MEAN), list(IMAGENET_STD))
+    elif params is not None:
+        from ..ops.reference import warp_norm_u8
+        out = warp_norm_u8(pix, meta, params, out_h, out_w, IMAGENET_MEAN, IMAGENET_STD, dtype=torch.float32).to(dev)
     else:
         ims = []
         for o, h, w in meta.tolist():
@@ -124,11 +148,20 @@ def gpu_pair_batch(batch, device, out_h: int, out_w: int):
     res["source_image"], res["target_image"] = out[:b], out[b:]
     return res
 
+
 class PFPascalDataset(Dataset):
     """PF-Pascal keypoint pairs (lib/pf_dataset.py:11-112)."""
 
     def __init__(self, csv_file, dataset_path, output_size=(240, 240), transform=None, category=None,
-                 pck_procedure="pf"):
+                 pck_procedure="pf", gpu_resize=False):
+        """``gpu_resize``: return the decoded images as HWC uint8 tensors of
+        their own size and skip ``transform`` (collate with
+        ``collate_uint8_pairs``, resize + normalise with ``gpu_pair_batch``);
+        points, sizes and ``L_pck`` are the same either way."""
+        if gpu_resize and pck_procedure == "scnet":
+            raise ValueError("pck_procedure='scnet' rescales the keypoints into a 224 x 224 frame that is not the "
+                             "pixel frame of the decoded image; it cannot be combined with gpu_resize")
+        self.gpu_resize = gpu_resize
         self.category_names = PF_CATEGORIES
         self.out_h, self.out_w = output_size
         pairs = pd.read_csv(csv_file)
@@ -152,6 +185,8 @@ class PFPascalDataset(Dataset):
     def get_image(self, name):
         image = read_image(os.path.join(self.dataset_path, name))
         im_size = torch.tensor(image.shape, dtype=torch.float32)
+        if self.gpu_resize:          # HWC uint8 as decoded; packed per batch by collate_uint8_pairs
+            return torch.from_numpy(np.ascontiguousarray(image)), im_size
         return resize_bilinear(to_chw_float(image), self.out_h, self.out_w), im_size
 
     @staticmethod
@@ -183,7 +218,7 @@ class PFPascalDataset(Dataset):
             raise ValueError(self.pck_procedure)
         sample = {"source_image": image_a, "target_image": image_b, "source_im_size": size_a,
                   "target_im_size": size_b, "source_points": pa, "target_points": pb, "L_pck": l_pck}
-        if self.transform:
+        if self.transform and not self.gpu_resize:
             sample = self.transform(sample)
         return sample
 

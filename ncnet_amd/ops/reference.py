@@ -21,6 +21,8 @@ depends on torch-0.3 semantics:
 * ``softmax_max_scores``  -- the weak-loss scores of train.py:121-134
 * ``keypoint_ce``         -- the keypoint-supervised loss (an extension; no
                              counterpart in the reference)
+* ``warp_norm_u8``        -- the augmenting input kernel's definition (an
+                             extension; no counterpart in the reference)
 
 Weight layout: Conv4d weights are stored the way the reference checkpoints
 store them, pre-permuted to ``[k, out, in, k, k, k]`` (lib/conv4d.py:75-77).
@@ -274,3 +276,38 @@ def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> 
     if sa.shape == sb.shape:
         return torch.mean(sa + sb) / 2
     return (sa.mean() + sb.mean()) / 2
+
+
+def warp_norm_u8(pixels: torch.Tensor, meta: torch.Tensor, params: torch.Tensor, oh: int, ow: int, mean, std,
+                 dtype: torch.dtype = torch.float64) -> torch.Tensor:
+    """The definition of the augmenting input kernel (csrc/dataprep.hip
+    ``warp_norm_u8``), written out: ``pixels`` the packed HWC uint8 bytes,
+    ``meta`` [N, 3] = (byte offset, H, W), ``params`` [N, 8] = (a0..a5, gain,
+    bias) -> [N, 3, oh, ow] in ``dtype``.  Output pixel (ox, oy) samples
+
+        sx = clamp(a0 ox + a1 oy + a2, 0, W - 1)      sy = clamp(a3 ox + a4 oy + a5, 0, H - 1)
+
+    (a NaN coordinate clamps to 0, as fmaxf / fminf do) bilinearly from its
+    four neighbours x0 = min(floor(sx), W - 1), x1 = min(x0 + 1, W - 1) (same
+    in y), then ``gain * ((v / 255 - mean[c]) / std[c]) + bias``.  fp64 (the
+    default) is the oracle of the kernel tests; ``gpu_pair_batch`` runs it in
+    fp32 for CPU tensors."""
+    pixels, meta = pixels.cpu(), meta.cpu()
+    q = params.detach().cpu().to(dtype)
+    m = torch.tensor(mean, dtype=dtype).view(3, 1, 1)
+    s = torch.tensor(std, dtype=dtype).view(3, 1, 1)
+    oy, ox = torch.meshgrid(torch.arange(oh, dtype=dtype), torch.arange(ow, dtype=dtype), indexing="ij")
+    out = torch.empty((meta.shape[0], 3, oh, ow), dtype=dtype)
+    for i, (off, h, w) in enumerate(meta.tolist()):
+        im = pixels[off:off + h * w * 3].view(h, w, 3).to(dtype)
+        a = q[i]
+        sx = torch.nan_to_num(a[0] * ox + a[1] * oy + a[2], nan=0.0).clamp(0, w - 1)
+        sy = torch.nan_to_num(a[3] * ox + a[4] * oy + a[5], nan=0.0).clamp(0, h - 1)
+        x0 = sx.floor().long().clamp(max=w - 1)
+        y0 = sy.floor().long().clamp(max=h - 1)
+        x1, y1 = (x0 + 1).clamp(max=w - 1), (y0 + 1).clamp(max=h - 1)
+        fx, fy = (sx - x0).unsqueeze(2), (sy - y0).unsqueeze(2)
+        v = ((1 - fy) * (1 - fx) * im[y0, x0] + (1 - fy) * fx * im[y0, x1]
+             + fy * (1 - fx) * im[y1, x0] + fy * fx * im[y1, x1]).permute(2, 0, 1)
+        out[i] = a[6] * ((v / 255 - m) / s) + a[7]
+    return out

@@ -15,6 +15,15 @@ Same flags and defaults as the reference, plus:
                        --synthetic N (synthetic pairs with known keypoints) or
                        --train_pairs_csv / --val_pairs_csv (test_pairs.csv
                        layout); every validation epoch also reports PCK@0.1
+  --gpu_input          --loss strong with --train_pairs_csv / --val_pairs_csv:
+                       the workers only decode; one uint8 copy and one HIP
+                       launch resize + normalise the batch on the GPU (what
+                       the weak path does by default on a GPU; with the weak
+                       loss the flag only matters on a CPU device, where it
+                       selects the same uint8 route through torch)
+  --augment            random rotation / zoom / shift / flip / contrast /
+                       brightness of the training batches in that same launch
+                       (--aug_* set the ranges); keypoints move with the pixels
   --metrics PATH       JSONL metrics (rank 0)
   --dtype bf16|fp32    backbone compute dtype of the default (bf16) NC mode
   --nc_precision bf16|mixed|fp32
@@ -57,6 +66,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from ncnet_amd.data import (ImagePairDataset, NormalizeImageDict, PFPascalDataset,  # noqa: E402
                             SyntheticCorrespondenceDataset, SyntheticPairDataset)
+from ncnet_amd.data.augment import PairAugment  # noqa: E402
 from ncnet_amd.data.datasets import collate_uint8_pairs, gpu_pair_batch  # noqa: E402
 from ncnet_amd.engine.checkpoint import capture_rng, load_checkpoint, restore_rng, save_checkpoint  # noqa: E402
 from ncnet_amd.engine.trainer import AsyncLossLog, Trainer, make_adam  # noqa: E402
@@ -107,10 +117,38 @@ def build_parser():
     p.add_argument("--train_pairs_csv", type=str, default="",
                    help="--loss strong: training pairs with keypoints (source,target,class,XA,YA,XB,YB)")
     p.add_argument("--val_pairs_csv", type=str, default="", help="--loss strong: validation pairs with keypoints")
+    p.add_argument("--gpu_input", action="store_true",
+                   help="--loss strong on pair CSVs: decode in the workers, resize + normalise the packed uint8 batch "
+                        "on the GPU; on a CPU device the same math runs through torch. The weak loss takes this route "
+                        "by default on a GPU: there the flag changes nothing, and on a CPU device it selects the "
+                        "uint8 route (torch) for the weak loss too")
+    p.add_argument("--augment", action="store_true",
+                   help="augment the training batches on the uint8 input path (implies --gpu_input): per-image random "
+                        "rotation, zoom, shift, contrast and brightness and a per-pair horizontal flip, in the same "
+                        "launch that resizes and normalises; keypoints are moved with the pixels, and a "
+                        "correspondence with a point outside its frame is dropped (-1). Validation batches are not "
+                        "augmented. The draws come from one generator per process seeded from (--seed, rank, first "
+                        "epoch): ranks differ, and a resumed run does NOT replay the draws of the uninterrupted run")
+    p.add_argument("--aug_rot_deg", type=float, default=15.0, help="rotation, uniform in +-DEG")
+    p.add_argument("--aug_scale", type=float, nargs=2, default=[0.8, 1.25], metavar=("LO", "HI"),
+                   help="zoom factor, log-uniform; below 1 zooms in")
+    p.add_argument("--aug_shift", type=float, default=0.1, help="shift, uniform in +-F of the source extent")
+    p.add_argument("--aug_flip", type=float, default=0.5, help="probability of a horizontal flip (per pair)")
+    p.add_argument("--aug_gain", type=float, nargs=2, default=[0.8, 1.2], metavar=("LO", "HI"),
+                   help="contrast about the ImageNet mean, log-uniform")
+    p.add_argument("--aug_bias", type=float, default=0.2, help="brightness in normalised units, uniform in +-B")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--segment_timing", action="store_true")
     p.add_argument("--profile", type=str, default="")
     return p
+
+
+def augment_seed(seed: int, rank: int, first_epoch: int) -> int:
+    """Seed of a process's augmentation generator: a mix of (--seed, rank, first
+    epoch) reduced into the range torch.Generator.manual_seed takes, for any
+    --seed.  Ranks of one run differ (their mixes differ by a multiple of
+    1000003 below 2^63)."""
+    return ((seed * 1000003 + rank) * 1000003 + first_epoch) % (1 << 63)
 
 
 class _Shard(torch.utils.data.Sampler):
@@ -136,6 +174,17 @@ def main(argv=None):
         raise SystemExit("--loss strong needs pairs with keypoints: give --synthetic N, or --train_pairs_csv and "
                          "--val_pairs_csv (test_pairs.csv layout: source,target,class,XA,YA,XB,YB); "
                          "the shipped train_pairs.csv / val_pairs.csv carry no keypoints")
+    for flag in ("augment", "gpu_input"):
+        if getattr(args, flag) and (args.synthetic or args.cpu_resize):
+            raise SystemExit(f"--{flag} works on the uint8 input path (decoded image files, resized on the device); "
+                             f"--{'synthetic' if args.synthetic else 'cpu_resize'} batches carry float images")
+    augment = None
+    if args.augment:
+        try:
+            augment = PairAugment(rot_deg=args.aug_rot_deg, scale=tuple(args.aug_scale), shift=args.aug_shift,
+                                  flip=args.aug_flip, gain=tuple(args.aug_gain), bias=args.aug_bias)
+        except ValueError as e:
+            raise SystemExit(f"--augment: {e}")
     ctx = init_distributed()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -165,10 +214,11 @@ def main(argv=None):
     optimizer = make_adam(params, args.lr)
 
     size = (args.image_size, args.image_size)
-    gpu_resize = ctx.device.type == "cuda" and not args.cpu_resize
+    uint8_input = args.gpu_input or args.augment       # asked for: on any device (CPU: the torch fallback)
+    gpu_resize = (ctx.device.type == "cuda" and not args.cpu_resize) or uint8_input
     if strong:
-        # keypoint datasets yield float images (no uint8 GPU-resize path)
-        gpu_resize = False
+        # keypoint datasets yield float images unless the uint8 path is asked for
+        gpu_resize = uint8_input
         if args.synthetic:
             train_set = SyntheticCorrespondenceDataset(args.synthetic, args.image_size, seed=1)
             test_set = SyntheticCorrespondenceDataset(max(2 * args.batch_size, args.synthetic // 8), args.image_size,
@@ -176,8 +226,9 @@ def main(argv=None):
         else:
             norm = NormalizeImageDict(["source_image", "target_image"])
             train_set = PFPascalDataset(args.train_pairs_csv, args.dataset_image_path, output_size=size,
-                                        transform=norm)
-            test_set = PFPascalDataset(args.val_pairs_csv, args.dataset_image_path, output_size=size, transform=norm)
+                                        transform=norm, gpu_resize=gpu_resize)
+            test_set = PFPascalDataset(args.val_pairs_csv, args.dataset_image_path, output_size=size, transform=norm,
+                                       gpu_resize=gpu_resize)
     elif args.synthetic:
         train_set = SyntheticPairDataset(args.synthetic, size, seed=1)
         test_set = SyntheticPairDataset(max(2 * args.batch_size, args.synthetic // 8), size, seed=2)
@@ -198,8 +249,12 @@ def main(argv=None):
                persistent_workers=nw > 0, prefetch_factor=4 if nw > 0 else None)
     train_loader = DataLoader(train_set, sampler=tr_sampler, **lkw)
     test_loader = DataLoader(test_set, sampler=te_sampler, **lkw)
+    aug_rng = torch.Generator() if augment is not None else None     # seeded below, once the first epoch is known
     if gpu_resize and not args.synthetic:
-        trainer_to_device = lambda batch: gpu_pair_batch(batch, ctx.device, size[0], size[1])  # noqa: E731
+        # training batches only (the Trainer sets model.training before it touches a loader): validation
+        # keeps the plain resize and its points, so its loss and PCK compare with an un-augmented run
+        trainer_to_device = lambda batch: gpu_pair_batch(  # noqa: E731
+            batch, ctx.device, size[0], size[1], augment=augment if model.training else None, generator=aug_rng)
     else:
         trainer_to_device = None
 
@@ -222,6 +277,8 @@ def main(argv=None):
         checkpoint_name = args.resume
         if ctx.is_main:
             print(f"Resumed from {args.resume} at epoch {start_epoch}")
+    if aug_rng is not None:
+        aug_rng.manual_seed(augment_seed(args.seed, ctx.rank, start_epoch))
     if ctx.is_main:
         print("Checkpoint name: " + checkpoint_name)
 
