@@ -1017,6 +1017,26 @@ int64_t debug_selftest(Tensor out) {
   return out.cpu().item<int>();
 }
 
+// LDS poison tier (csrc/lds_poison.hip): fill every CU's LDS with a 32-bit pattern on the
+// current stream of the current device
+void lds_poison(int64_t pattern, int64_t rounds) {
+  TORCH_CHECK(pattern >= 0 && pattern <= 0xFFFFFFFFLL, "lds_poison: pattern must be a 32-bit value");
+  TORCH_CHECK(rounds >= 1 && rounds <= 64, "lds_poison: rounds must be in 1..64");
+  ok(ncnet_lds_poison((unsigned int)pattern, (int)rounds, c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+     "lds_poison");
+}
+
+// out int32 [G, n_words]: what G workgroups find in their first n_words words of lds_bytes of dynamic LDS
+void lds_probe(Tensor out, int64_t lds_bytes) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  check(out, "out", at::kInt);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) >= 1 && out.size(0) <= 65535 && out.size(1) >= 1, "out must be [G, n_words]");
+  TORCH_CHECK(lds_bytes >= 4 && lds_bytes <= 163840 && lds_bytes % 4 == 0, "lds_bytes must be a multiple of 4 in 4..163840");
+  TORCH_CHECK(out.size(1) <= lds_bytes / 4, "n_words exceeds lds_bytes / 4");
+  ok(ncnet_lds_probe((int*)out.data_ptr(), (int)out.size(0), (int)out.size(1), (int)lds_bytes, cur_stream(out)),
+     "lds_probe");
+}
+
 void resize_norm_u8(Tensor src, Tensor meta, Tensor out, std::vector<double> mean, std::vector<double> stdv) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(src.device());
   check(src, "src", at::kByte); check(meta, "meta", at::kLong); check(out, "out", at::kFloat);
@@ -1235,6 +1255,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resize_norm_u8", &resize_norm_u8);
   m.def("warp_norm_u8", &warp_norm_u8);
   m.def("debug_selftest", &debug_selftest);
+  m.def("lds_poison", &lds_poison, py::arg("pattern"), py::arg("rounds") = 1);
+  m.def("lds_probe", &lds_probe);
   m.def("p3p_solve", &p3p_solve);
   m.def("p3p_ransac_batch", &p3p_ransac_batch, py::arg("rays"), py::arg("X"), py::arg("offsets"), py::arg("keys"),
         py::arg("thr_rad"), py::arg("max_iters"), py::arg("confidence"), py::arg("lo_iters"),

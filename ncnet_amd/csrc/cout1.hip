@@ -60,7 +60,8 @@ struct CT1 {
   static constexpr int ZPAD = 64;                        // floats before the staging rows (>= P K + P)
   static constexpr int LDS_RING = NW * NSLOT * SLOT;
   static constexpr int ZBUF = ZPAD + NT * ZCOLS;          // floats of one staging buffer (two)
-  static constexpr int ZBYTES = 2 * ZBUF * 4;
+  static constexpr int ZTAIL = 64;                       // floats after the second buffer (>= P L + P)
+  static constexpr int ZBYTES = (2 * ZBUF + ZTAIL) * 4;
   static constexpr int LDS = ROFF + (LDS_RING > ZBYTES ? LDS_RING : ZBYTES);
   static constexpr int WI = RI + KS - 1, WJ = RJ + KS - 1;   // input window (planes along i, j)
   static constexpr int NO = RI * RJ;                     // output planes per item
@@ -68,6 +69,9 @@ struct CT1 {
   static_assert(NT <= 32, "taps fit the 32 MFMA rows");
   static_assert(LDS <= 160 * 1024, "LDS");
   static_assert(ZPAD >= P * L + P, "the gather's lowest tap offset stays inside the staging area");
+  static_assert(ZTAIL >= P * L + P && ZTAIL <= ZPAD,
+                "the gather's highest tap offset (second buffer) stays inside the requested LDS");
+  static_assert(3 * ZPAD <= NW * 64, "one thread per pad float");
 };
 
 // DBG (scripts/probe/cout1_probe.hip only): 1 no epilogue, 2 no DMA waits,
@@ -181,6 +185,16 @@ __global__ __launch_bounds__(256, 1) void cout1_taps_fwd_kernel(const bf16* __re
     // ---- epilogue: per output plane, Z_o -> LDS staging [tap][col], shift-sum
     dma_wait_barrier<0>();   // every ring read and DMA done
     float* zs = (float*)(smem + C::ROFF) + C::ZPAD;
+    // The gather below reads all 25 taps of an output and drops the out-of-plane
+    // ones with a 0 / 1 multiplier; such a read lands in a neighbouring staging
+    // row (written by write_z), in the ZPAD before a buffer -- the first
+    // buffer's last taps reach the second buffer's ZPAD -- or in ZTAIL.  The
+    // pads alias the ring, so they are zeroed here, per item: every word the
+    // gather reads was then written in this launch, and 0 x (what an earlier
+    // kernel left in LDS: possibly NaN or Inf) can never reach Y.  Waves 0 / 1 /
+    // 2 take ZPAD of buffer 0, ZPAD of buffer 1 and ZTAIL; the barrier after
+    // write_z orders the stores before the first gather.
+    if (wave < 3 && lane < (wave < 2 ? C::ZPAD : C::ZTAIL)) zs[wave * C::ZBUF - C::ZPAD + lane] = 0.f;
     // this thread's outputs o = tid + 256 m: per-tap validity as row / column
     // masks (1 / 0) and one staging base; tap (dk, dl) of output (k, l) reads
     // zs[tap][(k + dk - P) L + l + dl - P] = base + tap ZCOLS + dk L + dl - (P L + P)

@@ -155,6 +155,14 @@ int ncnet_reduce_cols(const float* const* src, float* const* dst, const int* con
 // Sanitizer-tier self test: out[0] = 1 in release, 0 (after an NCNET_CHECK line) in the debug build.
 int ncnet_debug_selftest(int* out, hipStream_t stream);
 
+// ---- LDS poison tier, test support (csrc/lds_poison.hip) ------------------
+// Fill all 160 KiB of LDS of every CU with `pattern`: rounds (1..64, else -3) x CU-count
+// workgroups that each own a whole CU's LDS.
+int ncnet_lds_poison(unsigned int pattern, int rounds, hipStream_t stream);
+// out int32 [G, n_words]: the first n_words words of each of G workgroups' uninitialised
+// dynamic LDS of lds_bytes (a multiple of 4, <= 163840; n_words <= lds_bytes / 4; else -3).
+int ncnet_lds_probe(int* out, int G, int n_words, int lds_bytes, hipStream_t stream);
+
 // ---- correlation (csrc/corr.hip) ------------------------------------------
 // y dtype: bf16 (fp8_scale == 0; ylo: optional low half) or OCP fp8 e4m3 scaled by fp8_scale.
 // y_f16: y is IEEE half (no lo half, no fp8).  inv_norm [rows] or null.

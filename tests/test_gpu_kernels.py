@@ -176,7 +176,7 @@ def test_conv16_blk_fwd(ks, shape, cin, relu):
                                           ((2, 4, 3, 25, 25), 10, 1)])
 def test_cout1_taps_fwd(shape, cin, relu):
     """Cout=1 conv with the 25 in-plane taps on the MFMA rows (csrc/cout1.hip:
-    2 x 2 output-plane items, odd I / J edges, the in-plane shift-sum through
+    1 x 3 output-plane items, odd I / J edges, the in-plane shift-sum through
     LDS) vs the fp64 Conv4d oracle on the same bf16 operands, and bit for bit
     across two launches; a one-tap weight perturbation must be detected."""
     from ncnet_amd.ops.packing import cout1_taps_weights
