@@ -721,6 +721,84 @@ void kploss_bwd(Tensor x, Tensor cells, Tensor wts, Tensor valid, Tensor lse, Te
                       (int)B, (int)N, (int)R, (int)C, cur_stream(x)), "kploss_bwd");
 }
 
+// dense correspondence loss (csrc/densece.hip): warp_maps fp64 [B, 2, 12]; the table is cells int32 / wts fp32
+// [B, 2, 4, n], valid int32 [B, 2, n] with n = max(hA * wA, hB * wB)
+static void check_densece_table(const char* fn, Tensor cells, Tensor wts, Tensor valid, int64_t B, int64_t n) {
+  TORCH_CHECK(B >= 1 && n >= 1 && B * 2 * n < (int64_t)1 << 40 && n < (int64_t)1 << 31, fn, ": bad or too large geometry");
+  check(cells, "cells", at::kInt); check_shape(cells, "cells", {B, 2, 4, n});
+  check(wts, "wts", at::kFloat); check_shape(wts, "wts", {B, 2, 4, n});
+  check(valid, "valid", at::kInt); check_shape(valid, "valid", {B, 2, n});
+}
+
+void densece_table(Tensor maps, int64_t hA, int64_t wA, int64_t hB, int64_t wB, Tensor cells, Tensor wts,
+                   Tensor valid) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(maps.device());
+  check(maps, "warp_maps", at::kDouble);
+  TORCH_CHECK(maps.dim() == 3 && maps.size(1) == 2 && maps.size(2) == 12, "densece_table: warp_maps must be [B, 2, 12]");
+  TORCH_CHECK(hA >= 1 && wA >= 1 && hB >= 1 && wB >= 1 && hA * wA < (int64_t)1 << 31 && hB * wB < (int64_t)1 << 31,
+              "densece_table: bad grid ", hA, "x", wA, " / ", hB, "x", wB);
+  const int64_t B = maps.size(0), n = std::max(hA * wA, hB * wB);
+  check_densece_table("densece_table", cells, wts, valid, B, n);
+  ok(ncnet_densece_table((double*)maps.data_ptr(), (int)B, (int)hA, (int)wA, (int)hB, (int)wB, (int)n,
+                         (int*)cells.data_ptr(), (float*)wts.data_ptr(), (int*)valid.data_ptr(), cur_stream(maps)),
+     "densece_table");
+}
+
+// x [B, R, C]; rmax / rse [B, R], cmax / cse [B, C] from stats2d(sum_kind = 1); writes lse / term [B, 2, n]
+void densece_fwd(Tensor x, Tensor cells, Tensor wts, Tensor valid, Tensor rmax, Tensor rse, Tensor cmax, Tensor cse,
+                 Tensor lse, Tensor term) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(x, "x", at::kFloat);
+  TORCH_CHECK(x.dim() == 3, "densece_fwd: x must be [B, R, C]");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2), n = std::max(R, C);
+  TORCH_CHECK(R >= 1 && C >= 1, "densece_fwd: empty volume");
+  check_densece_table("densece_fwd", cells, wts, valid, B, n);
+  check(rmax, "rmax", at::kFloat); check_shape(rmax, "rmax", {B, R});
+  check(rse, "rse", at::kFloat); check_shape(rse, "rse", {B, R});
+  check(cmax, "cmax", at::kFloat); check_shape(cmax, "cmax", {B, C});
+  check(cse, "cse", at::kFloat); check_shape(cse, "cse", {B, C});
+  check(lse, "lse", at::kFloat); check_shape(lse, "lse", {B, 2, n});
+  check(term, "term", at::kFloat); check_shape(term, "term", {B, 2, n});
+  ok(ncnet_densece_fwd((float*)x.data_ptr(), (int*)cells.data_ptr(), (float*)wts.data_ptr(), (int*)valid.data_ptr(),
+                       (float*)rmax.data_ptr(), (float*)rse.data_ptr(), (float*)cmax.data_ptr(), (float*)cse.data_ptr(),
+                       (int)B, (int)R, (int)C, (int)n, (float*)lse.data_ptr(), (float*)term.data_ptr(), cur_stream(x)),
+     "densece_fwd");
+}
+
+// term fp32 / valid int32 [B, 2, n] -> out [3] = (loss, 1 / (2 max(1, N_A)), 1 / (2 max(1, N_B)))
+void densece_reduce(Tensor term, Tensor valid, Tensor out) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(term.device());
+  check(term, "term", at::kFloat);
+  TORCH_CHECK(term.dim() == 3 && term.size(1) == 2, "densece_reduce: term must be [B, 2, n]");
+  const int64_t B = term.size(0), n = term.size(2);
+  TORCH_CHECK(B >= 1 && n >= 1 && B < (int64_t)1 << 30 && n < (int64_t)1 << 31, "densece_reduce: bad or too large geometry");
+  check(valid, "valid", at::kInt); check_shape(valid, "valid", {B, 2, n});
+  check(out, "out", at::kFloat); check_shape(out, "out", {3});
+  Tensor part = at::empty({B, 2, 2}, term.options().dtype(at::kDouble));
+  ok(ncnet_densece_reduce((float*)term.data_ptr(), (int*)valid.data_ptr(), (int)B, (int)n, (double*)part.data_ptr(),
+                          (float*)out.data_ptr(), cur_stream(term)), "densece_reduce");
+}
+
+// gx [B, R, C] = gscale * dloss/dx (every element written); lse: densece_fwd's (+inf marks an invalid line);
+// scales [3]: the forward's out
+void densece_bwd(Tensor x, Tensor cells, Tensor wts, Tensor lse, Tensor scales, Tensor gx,
+                 c10::optional<Tensor> gscale) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check(x, "x", at::kFloat); check(gx, "gx", at::kFloat);
+  TORCH_CHECK(x.dim() == 3 && gx.sizes() == x.sizes(), "densece_bwd: x and gx must be [B, R, C]");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2), n = std::max(R, C);
+  TORCH_CHECK(B >= 1 && R >= 1 && C >= 1 && B * 2 * n < (int64_t)1 << 40 && n < (int64_t)1 << 31,
+              "densece_bwd: bad or too large geometry");
+  check(cells, "cells", at::kInt); check_shape(cells, "cells", {B, 2, 4, n});
+  check(wts, "wts", at::kFloat); check_shape(wts, "wts", {B, 2, 4, n});
+  check(lse, "lse", at::kFloat); check_shape(lse, "lse", {B, 2, n});
+  check(scales, "scales", at::kFloat); check_shape(scales, "scales", {3});
+  if (gscale.has_value()) { check(*gscale, "gscale", at::kFloat); TORCH_CHECK(gscale->numel() == 1, "gscale: one element"); }
+  ok(ncnet_densece_bwd((float*)x.data_ptr(), (int*)cells.data_ptr(), (float*)wts.data_ptr(), (float*)lse.data_ptr(),
+                       (float*)scales.data_ptr(), opt_ptr<float>(gscale), (float*)gx.data_ptr(), (int)B, (int)R, (int)C,
+                       (int)n, cur_stream(x)), "densece_bwd");
+}
+
 void maxpool4d(Tensor x, Tensor y, Tensor code, int64_t ks) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16));
@@ -1248,6 +1326,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kploss_fwd", &kploss_fwd);
   m.def("kploss_bwd", &kploss_bwd, py::arg("x"), py::arg("cells"), py::arg("wts"), py::arg("valid"), py::arg("lse"),
         py::arg("scale"), py::arg("gx"), py::arg("gscale") = py::none());
+  m.def("densece_table", &densece_table);
+  m.def("densece_fwd", &densece_fwd);
+  m.def("densece_reduce", &densece_reduce);
+  m.def("densece_bwd", &densece_bwd, py::arg("x"), py::arg("cells"), py::arg("wts"), py::arg("lse"), py::arg("scales"),
+        py::arg("gx"), py::arg("gscale") = py::none());
   m.def("maxpool4d", &maxpool4d);
   m.def("transpose", &transpose);
   m.def("nc_fused_k3", &nc_fused_k3);

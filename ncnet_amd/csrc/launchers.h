@@ -242,6 +242,28 @@ int ncnet_kploss_fwd(const float* x, const float* sp, const float* tp, const flo
 int ncnet_kploss_bwd(const float* x, const int* cells, const float* wts, const int* valid, const float* lse,
                      const float* scale, const float* gscale, float* gx, int B, int N, int R, int C, hipStream_t s);
 
+// ---- dense correspondence loss (csrc/densece.hip) ---------------------------
+// maps fp64 [B, 2, 12]: per image and side (0: the A cells, 1: the B cells) two affine maps (m00, m01, c0,
+// m10, m11, c1) on unit coordinates, entries 0..5 into the other view, 6..11 into the source image.
+// Writes the struct-of-arrays table with n = max(hA*wA, hB*wB): cells int32 / wts fp32 [B, 2, 4, n] (side 0:
+// cells of the B grid, side 1: of the A grid), valid int32 [B, 2, n]; zero past a side's cell count and for
+// invalid cells.
+int ncnet_densece_table(const double* maps, int B, int hA, int wA, int hB, int wB, int n, int* cells, float* wts,
+                        int* valid, hipStream_t s);
+// x [B, R, C] fp32 with the table above and the stats2d statistics (sum_kind 1) rmax / rse [B, R],
+// cmax / cse [B, C]: lse [B, 2, n] = max + log(se) per row / column, term [B, 2, n] = lse - sum_k w_k x[cell_k]
+// (for an invalid cell and past a side's cell count: term 0, lse +inf, which is what the backward reads).
+int ncnet_densece_fwd(const float* x, const int* cells, const float* wts, const int* valid, const float* rmax,
+                      const float* rse, const float* cmax, const float* cse, int B, int R, int C, int n, float* lse,
+                      float* term, hipStream_t s);
+// term / valid [B, 2, n] -> out [3] = (loss, 1 / (2 max(1, N_A)), 1 / (2 max(1, N_B))); part: 4 B doubles of
+// workspace.  Fixed order (one wave per (image, side), then one wave).
+int ncnet_densece_reduce(const float* term, const int* valid, int B, int n, double* part, float* out, hipStream_t s);
+// gx [B, R, C] = gscale[0] (or 1: null) * dloss/dx from the table (cells, wts), lse and scales = the forward's out [3];
+// every element is written.  16-byte access when x and gx are 16-byte aligned, else scalar.
+int ncnet_densece_bwd(const float* x, const int* cells, const float* wts, const float* lse,
+                      const float* scales, const float* gscale, float* gx, int B, int R, int C, int n, hipStream_t s);
+
 // ---- guarded flat Adam (csrc/optim.hip) -----------------------------------
 // g may be longer than p (trailing loss-indicator slot); count / skipped int32 [1], step fp32 [1].
 int ncnet_nonfinite_count(const float* g, long long n, int* count, hipStream_t s);

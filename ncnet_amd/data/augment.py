@@ -184,3 +184,55 @@ def transform_pair_points(source_points, target_points, params, oh: int, ow: int
     keep = ((sp != -1).all(1) & (tp != -1).all(1)).unsqueeze(1)
     return (torch.where(keep, sp, torch.full_like(sp, -1.0)),
             torch.where(keep, tp, torch.full_like(tp, -1.0)))
+
+
+def view_maps(params: torch.Tensor, meta: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
+    """``warp_maps`` [B, 2, 12] fp64 of a two-view batch (the table of
+    ``ops/reference.py dense_ce``): ``params`` [2B, 8] and ``meta`` [2B, 3] =
+    (byte offset, H, W) hold view A of image b in row b and view B in row
+    B + b, both views sampling the SAME source image.
+
+    With ``p -> A_v p + t_v`` the pixel map of view v (output pixel -> source
+    position), ``D_o = diag(ow - 1, oh - 1)`` and ``D_s = diag(W - 1, H - 1)``,
+    on unit coordinates (pixel / (extent - 1)):
+
+        view -> source:   u -> D_s^-1 (A_v D_o u + t_v)                 entries 6..11
+        A -> B:           u -> D_o^-1 A_b^-1 (A_a D_o u + t_a - t_b)    entries 0..5, row [b, 0]
+        B -> A:           likewise with a and b swapped                 entries 0..5, row [b, 1]
+
+    Each map is stored as (m00, m01, c0, m10, m11, c1).  Composed in fp64 on
+    the host.  A singular view map (an image with H < 2 or W < 2, or oh < 2 or
+    ow < 2) has no inverse: ``ValueError``, as ``transform_points``."""
+    q = params.detach().cpu().to(torch.float64)
+    meta = meta.cpu()
+    n = q.shape[0]
+    if n % 2 or meta.shape[0] != n:
+        raise ValueError(f"a two-view batch has 2B parameter and meta rows, got {n} and {meta.shape[0]}")
+    b = n // 2
+    if not torch.equal(meta[:b, 1:], meta[b:, 1:]):
+        raise ValueError("the two views of an image must share its size")
+    A = torch.stack((q[:, [0, 1]], q[:, [3, 4]]), 1)                                  # [2B, 2, 2]
+    t = q[:, [2, 5]]
+    det = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+    d_s = torch.stack((meta[:, 2] - 1, meta[:, 1] - 1), 1).to(torch.float64)          # (W-1, H-1)
+    bad = (det == 0) | (d_s == 0).any(1)
+    if oh < 2 or ow < 2 or bool(bad.any()):
+        which = f"view {int(torch.nonzero(bad)[0])}" if bool(bad.any()) else f"an output of {oh} x {ow}"
+        raise ValueError(f"{which} of the batch has a singular sampling map: an image with H < 2 or W < 2, or an "
+                         "output with oh < 2 or ow < 2, has no pixel frame to map cells in")
+    inv = torch.stack((torch.stack((A[:, 1, 1], -A[:, 0, 1]), 1),
+                       torch.stack((-A[:, 1, 0], A[:, 0, 0]), 1)), 1) / det.view(-1, 1, 1)
+    d_o = torch.tensor([ow - 1.0, oh - 1.0], dtype=torch.float64)
+    other = torch.cat((torch.arange(b, n), torch.arange(0, b)))                       # the other view of each row
+    # into the other view: D_o^-1 inv_o (A D_o u + t - t_o)
+    M = (inv[other] @ A) * d_o.view(1, 1, 2) / d_o.view(1, 2, 1)
+    c = (inv[other] @ (t - t[other]).unsqueeze(2)).squeeze(2) / d_o
+    # into the source image: D_s^-1 (A D_o u + t)
+    Ms = A * d_o.view(1, 1, 2) / d_s.unsqueeze(2)
+    cs = t / d_s
+    rows = torch.stack((M[:, 0, 0], M[:, 0, 1], c[:, 0], M[:, 1, 0], M[:, 1, 1], c[:, 1],
+                        Ms[:, 0, 0], Ms[:, 0, 1], cs[:, 0], Ms[:, 1, 0], Ms[:, 1, 1], cs[:, 1]), 1)   # [2B, 12]
+    out = torch.stack((rows[:b], rows[b:]), 1).contiguous()
+    if not bool(torch.isfinite(out).all()):
+        raise ValueError("non-finite view maps (check the augmentation parameters)")
+    return out

@@ -149,6 +149,140 @@ def gpu_pair_batch(batch, device, out_h: int, out_w: int, augment=None, generato
     return res
 
 
+class SingleImageDataset(Dataset):
+    """Single images for warp-supervised training (``train.py --loss warp``):
+    item i is ``{"image": HWC uint8 as decoded}`` of ``names[i]`` under
+    ``image_root`` -- the workers only decode; the two views of every image are
+    cut on the device (``gpu_view_batch``).  Collate with ``collate_uint8_images``."""
+
+    def __init__(self, image_root, names):
+        self.image_root = image_root
+        self.names = list(names)
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, idx):
+        image = read_image(os.path.join(self.image_root, self.names[idx]))
+        return {"image": torch.from_numpy(np.ascontiguousarray(image))}
+
+
+class SyntheticImageDataset(Dataset):
+    """Low-pass noise uint8 images of a fixed size (``train.py --loss warp
+    --synthetic N``): item i is a sum of upsampled noise octaves, deterministic
+    per (seed, index), as ``{"image": HWC uint8}``."""
+
+    def __init__(self, n: int = 64, hw=(400, 400), seed: int = 0):
+        self.length = int(n)
+        self.h, self.w = (hw, hw) if isinstance(hw, int) else hw
+        self.seed = seed
+
+    def __len__(self):
+        return self.length
+
+    def __getitem__(self, idx):
+        if not 0 <= idx < self.length:
+            raise IndexError(idx)
+        g = torch.Generator().manual_seed(self.seed * 100003 + int(idx))
+        # the octaves are summed on the finest one's 48 x 48 grid and upsampled once: a worker
+        # makes an image in about the time it decodes a JPEG of that size
+        low = torch.zeros(1, 3, 48, 48)
+        for cells, amp in ((6, 1.0), (12, 0.6), (24, 0.35), (48, 0.2)):
+            noise = torch.randn(1, 3, cells, cells, generator=g)
+            low += amp * torch.nn.functional.interpolate(noise, size=(48, 48), mode="bicubic", align_corners=True)
+        low = low / low.std() * 60.0 + 128.0
+        out = torch.nn.functional.interpolate(low, size=(self.h, self.w), mode="bilinear", align_corners=True)[0]
+        image = out.clamp(0, 255).round().to(torch.uint8)
+        return {"image": image.permute(1, 2, 0).contiguous()}
+
+
+def collate_uint8_images(samples):
+    """Batch of single-image samples (runs in the DataLoader workers): the
+    decoded HWC uint8 pixels of the B images packed into ONE byte buffer
+    ``pixels`` with ``pixel_meta`` [B, 3] = (byte offset, H, W)."""
+    imgs = [s["image"] for s in samples]
+    sizes = [int(x.numel()) for x in imgs]
+    offs = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)
+    meta = torch.tensor([[o, x.shape[0], x.shape[1]] for o, x in zip(offs, imgs)], dtype=torch.int64)
+    return {"pixels": torch.cat([x.reshape(-1) for x in imgs]), "pixel_meta": meta}
+
+
+VIEW_POINT_GRID = 25      # gpu_view_batch(with_points=True): the A-cell centres of a 25 x 25 grid
+
+
+def gpu_view_batch(batch, device, out_h: int, out_w: int, augment, generator, with_points: bool = False):
+    """Two random views of every image of a ``collate_uint8_images`` batch,
+    with their dense ground-truth correspondence (``train.py --loss warp``).
+
+    The meta rows are duplicated to [2B, 3] with the SAME byte offsets (view A
+    of image b is row b, view B row B + b; the pixels are not copied),
+    ``draw_params`` draws one row per view (its per-pair flip applies to both
+    views of an image, which keeps the correspondence a plain affine map), the
+    bytes are uploaded once and ONE ``warp_norm_u8`` launch cuts, resizes,
+    jitters and normalises all 2B views (on CPU tensors: the fp32 torch form
+    of the same definition).  The launch takes the rows interleaved (A0, B0,
+    A1, B1, ...): the kernel's contract, asserted by its bounds-checked build,
+    is a table of non-decreasing byte offsets; the two images returned are
+    therefore strided views of one [B, 2, 3, out_h, out_w] buffer.  Returns ``source_image`` (view A), ``target_image``
+    (view B) [B, 3, out_h, out_w] and ``warp_maps`` [B, 2, 12] fp64
+    (``data.augment.view_maps``) on ``device``.
+
+    ``with_points``: also ``source_points`` / ``target_points`` [B, 2, 625] --
+    the A-cell centres of a 25 x 25 grid and their images in view B, (x, y) in
+    1-based pixels, ``-1`` where the cell is not valid (``dense_targets``) --
+    ``source_im_size`` / ``target_im_size`` = (out_h, out_w, 3) and ``L_pck`` =
+    max(out_h, out_w): the fields ``engine.trainer.batch_pck`` scores."""
+    from .augment import draw_params, view_maps
+    from .transforms import IMAGENET_MEAN, IMAGENET_STD
+    from ..ops import _ext
+    if augment is None:
+        raise ValueError("gpu_view_batch needs a PairAugment: the two views differ only by their random maps")
+    pix, meta = batch["pixels"], batch["pixel_meta"]
+    b = meta.shape[0]
+    ends = meta[:, 0] + meta[:, 1] * meta[:, 2] * 3
+    if b < 1 or int(ends.max()) > pix.numel() or int(meta[:, 1:].min()) < 1 or int(meta[:, 0].min()) < 0:
+        raise ValueError("malformed pixel table")
+    meta2 = torch.cat((meta, meta), 0)
+    params = draw_params(meta2, out_h, out_w, augment, generator)
+    maps = view_maps(params, meta2, out_h, out_w)
+    dev = torch.device(device)
+    res = {"warp_maps": maps.to(dev, non_blocking=True)}
+    if with_points:
+        from ..ops.reference import dense_targets
+        g = VIEW_POINT_GRID
+        _, _, ok, _, _, _ = dense_targets(maps, g, g, g, g)
+        i, j = torch.meshgrid(torch.arange(g, dtype=torch.float64), torch.arange(g, dtype=torch.float64),
+                              indexing="ij")
+        ux, uy = (j / (g - 1)).reshape(1, -1), (i / (g - 1)).reshape(1, -1)
+        m = maps[:, 0]
+        qx = m[:, 0:1] * ux + m[:, 1:2] * uy + m[:, 2:3]
+        qy = m[:, 3:4] * ux + m[:, 4:5] * uy + m[:, 5:6]
+        ext = torch.tensor([out_w - 1.0, out_h - 1.0], dtype=torch.float64).view(1, 2, 1)
+        sp = torch.stack((ux.expand(b, -1), uy.expand(b, -1)), 1) * ext + 1.0
+        tp = torch.stack((qx, qy), 1) * ext + 1.0
+        keep = ok.unsqueeze(1)
+        size = torch.tensor([float(out_h), float(out_w), 3.0]).expand(b, 3).contiguous()
+        pts = {"source_points": torch.where(keep, sp, torch.full_like(sp, -1.0)).float(),
+               "target_points": torch.where(keep, tp, torch.full_like(tp, -1.0)).float(),
+               "source_im_size": size, "target_im_size": size.clone(),
+               "L_pck": torch.full((b, 1), float(max(out_h, out_w)))}
+        res.update({k: v.to(dev, non_blocking=True) for k, v in pts.items()})
+    order = torch.arange(2 * b).view(2, b).t().reshape(-1)                    # A0, B0, A1, B1, ...
+    meta_k, params_k = meta2[order].contiguous(), params[order].contiguous()
+    pix_d = pix.to(dev, non_blocking=True) if dev.type == "cuda" else None   # the batch's ONE pixel copy
+    if pix_d is not None and _ext.use_hip(pix_d):
+        out = torch.empty((2 * b, 3, out_h, out_w), dtype=torch.float32, device=dev)
+        _ext.ext().warp_norm_u8(pix_d, meta_k.to(dev, non_blocking=True), params_k.to(dev, non_blocking=True), out,
+                                list(IMAGENET_MEAN), list(IMAGENET_STD))
+    else:
+        from ..ops.reference import warp_norm_u8
+        out = warp_norm_u8(pix, meta_k, params_k, out_h, out_w, IMAGENET_MEAN, IMAGENET_STD,
+                           dtype=torch.float32).to(dev)
+    out = out.view(b, 2, 3, out_h, out_w)
+    res["source_image"], res["target_image"] = out[:, 0], out[:, 1]
+    return res
+
+
 class PFPascalDataset(Dataset):
     """PF-Pascal keypoint pairs (lib/pf_dataset.py:11-112)."""
 

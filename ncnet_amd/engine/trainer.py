@@ -1,5 +1,6 @@
 """Weakly-supervised training loop (train.py:110-205), DP-aware; optionally
-keypoint-supervised (``Trainer(loss='strong')``, an extension beyond the reference).
+keypoint-supervised (``Trainer(loss='strong')``) or warp-supervised
+(``Trainer(loss='warp')``), both extensions beyond the reference.
 
 Differences from the reference, all semantics-preserving:
 * the negative pass reuses the positive-pass backbone features rolled by one
@@ -28,7 +29,7 @@ import torch
 
 from .. import config as _config
 
-from ..ops.loss import strong_loss_from_corr, weak_loss_from_corr
+from ..ops.loss import strong_loss_from_corr, warp_loss_from_corr, weak_loss_from_corr
 from ..parallel.dist import DistContext, GradBucket, all_reduce_mean
 from ..utils.timing import active as active_timer, segment
 
@@ -133,7 +134,21 @@ def strong_loss_from_features(model, feats, batch) -> torch.Tensor:
     return strong_loss_from_corr(model.match_volumes_from_features(f, hw, b), batch)
 
 
+def warp_loss(model, batch) -> torch.Tensor:
+    """Dense correspondence loss (ops/reference.py dense_ce) of a two-view
+    batch (data/datasets.py gpu_view_batch): the model's positive volumes
+    against the batch's ``warp_maps``."""
+    return warp_loss_from_corr(_positive_volumes(model, batch), batch)
+
+
+def warp_loss_from_features(model, feats, batch) -> torch.Tensor:
+    """warp_loss on backbone features ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
+    f, hw, b = feats
+    return warp_loss_from_corr(model.match_volumes_from_features(f, hw, b), batch)
+
+
 _KEYPOINT_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size", "L_pck")
+_WARP_FIELDS = ("warp_maps",) + _KEYPOINT_FIELDS
 
 
 def batch_pck(corr4d, batch, alpha: float = 0.1) -> torch.Tensor:
@@ -214,17 +229,19 @@ class TrunkPrefetcher:
 
 
 class Trainer:
-    """``loss``: ``'weak'`` (the reference's objective, the default) or
+    """``loss``: ``'weak'`` (the reference's objective, the default),
     ``'strong'`` -- the keypoint-supervised loss on batches that carry
-    ``source_points`` / ``target_points`` / ``*_im_size``.  Under data
-    parallelism each rank normalises the strong loss by its OWN number of valid
-    keypoints and the gradients are then averaged over ranks as for the weak
-    loss (so ranks, not keypoints, weigh equally)."""
+    ``source_points`` / ``target_points`` / ``*_im_size`` -- or ``'warp'`` --
+    the dense correspondence loss on two-view batches that carry ``warp_maps``
+    (``data.datasets.gpu_view_batch``).  Under data parallelism each rank
+    normalises the strong / warp loss by its OWN number of valid keypoints /
+    cells and the gradients are then averaged over ranks as for the weak loss
+    (so ranks, not keypoints, weigh equally)."""
 
     def __init__(self, model, optimizer, ctx: DistContext, normalization="softmax", nan_guard=True,
                  metrics_path: str | None = None, fault_step: int | None = None, loss: str = "weak"):
-        if loss not in ("weak", "strong"):
-            raise ValueError(f"loss must be 'weak' or 'strong', got {loss!r}")
+        if loss not in ("weak", "strong", "warp"):
+            raise ValueError(f"loss must be 'weak', 'strong' or 'warp', got {loss!r}")
         self.loss = loss
         self.model = model
         self.opt = optimizer
@@ -245,8 +262,8 @@ class Trainer:
         self.fault_step = fault_step if fault_step is not None else _config.RUNTIME.fault_step
         self.prefetch = TrunkPrefetcher(model)
         self.batch_to_device = None       # optional hook: host batch -> device batch (train.py: GPU resize)
-        self._pck = []                    # per-sample PCK of the evaluation steps (loss='strong')
-        self.last_pck = None              # PCK@0.1 of the last evaluation epoch (loss='strong')
+        self._pck = []                    # per-sample PCK of the evaluation steps (loss='strong' / 'warp')
+        self.last_pck = None              # PCK@0.1 of the last evaluation epoch (loss='strong' / 'warp')
 
     def _move(self, batch):
         if self.batch_to_device is not None:
@@ -277,17 +294,20 @@ class Trainer:
         with segment("forward"):
             feats = self.prefetch.take(batch)
             self.prefetch.submit(next_batch)
-            if self.loss == "strong":
+            if self.loss in ("strong", "warp"):
                 if self.prefetch.enabled:
-                    # the keypoint tensors were moved on the prefetch stream with the images
-                    # (to_device); take() made the main stream wait for it, and like the
+                    # the keypoint tensors / view maps were moved on the prefetch stream with the
+                    # images (to_device); take() made the main stream wait for it, and like the
                     # features they must not be recycled there while this step reads them
                     main = torch.cuda.current_stream(self.prefetch.stream.device)
-                    for k in _KEYPOINT_FIELDS:
+                    for k in _WARP_FIELDS if self.loss == "warp" else _KEYPOINT_FIELDS:
                         v = batch.get(k)
                         if torch.is_tensor(v) and v.is_cuda:
                             v.record_stream(main)
-                loss = strong_loss_from_features(self.model, feats, batch)
+                if self.loss == "warp":
+                    loss = warp_loss_from_features(self.model, feats, batch)
+                else:
+                    loss = strong_loss_from_features(self.model, feats, batch)
             else:
                 loss = weak_loss_from_features(self.model, feats, self.normalization)
         with segment("backward"):
@@ -336,6 +356,11 @@ class Trainer:
             if "L_pck" in batch:              # PCK of the same volume, summarised per epoch by process_epoch
                 self._pck.append(batch_pck(vol, batch))
             return strong_loss_from_corr(vol, batch).detach()
+        if self.loss == "warp":
+            vol = _positive_volumes(self.model, batch)
+            if "L_pck" in batch and "source_points" in batch:
+                self._pck.append(batch_pck(vol, batch))
+            return warp_loss_from_corr(vol, batch).detach()
         return weak_loss(self.model, batch, self.normalization).detach()
 
     def _log(self, rec: dict):
@@ -392,7 +417,7 @@ class Trainer:
         mean = float(all_reduce_mean(total / max(n, 1), self.ctx))
         if self.ctx.is_main:
             print(f"{mode.capitalize()} set: Average loss: {mean:.4f}", flush=True)
-        if not is_train and self.loss == "strong" and self._pck:
+        if not is_train and self.loss in ("strong", "warp") and self._pck:
             # mean over this rank's samples with keypoints, then over ranks
             pck = torch.cat(self._pck).float()
             self._pck = []

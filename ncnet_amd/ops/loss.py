@@ -14,6 +14,10 @@ closed-form backward kernel:
 ``strong_loss_from_corr`` is the keypoint-supervised objective (an extension
 beyond the reference; ``reference.keypoint_ce``) on the fused forward /
 closed-form backward kernels of csrc/kploss.hip.
+
+``warp_loss_from_corr`` is the dense correspondence objective of two warped
+views of one image (``reference.dense_ce``) on the kernels of csrc/densece.hip
+and the same single-pass statistics.
 """
 from __future__ import annotations
 
@@ -163,6 +167,65 @@ def strong_loss_from_corr(corr4d: torch.Tensor, batch) -> torch.Tensor:
         _ext.count("kploss")
         return KeypointCEFn.apply(corr4d.reshape(b, ha * wa, hb * wb), sp, tp, ssz, tsz, (ha, wa, hb, wb))
     return ref.keypoint_ce(corr4d, sp, tp, ssz, tsz)
+
+
+class DenseCEFn(torch.autograd.Function):
+    """ops/reference.py dense_ce on the HIP kernels of csrc/densece.hip: the
+    forward builds the target table on the device, takes the row / column
+    log-sum-exps from the one-pass stats2d statistics and reduces the terms in
+    a fixed order; it saves the table, the log-sum-exps (+inf for an invalid
+    line: the backward then needs no flag) and ``out`` = (loss, 1 / (2 N_A),
+    1 / (2 N_B)).  The backward is the closed form, one pass over
+    the volume, scaled by the incoming gradient inside the kernel (no host sync)."""
+
+    @staticmethod
+    def forward(ctx, x3, maps, grid):
+        x3 = x3.float().contiguous()
+        C = _ext.ext()
+        B, R, Cc = x3.shape
+        n = max(R, Cc)
+        dev = x3.device
+        cells = torch.empty((B, 2, 4, n), dtype=torch.int32, device=dev)
+        wts = torch.empty((B, 2, 4, n), dtype=torch.float32, device=dev)
+        valid = torch.empty((B, 2, n), dtype=torch.int32, device=dev)
+        lse = torch.empty((B, 2, n), dtype=torch.float32, device=dev)
+        term = torch.empty((B, 2, n), dtype=torch.float32, device=dev)
+        out = torch.empty(3, dtype=torch.float32, device=dev)
+        C.densece_table(maps, *grid, cells, wts, valid)
+        rmax, _, rse, cmax, _, cse = _row_col_stats(x3, 1)
+        C.densece_fwd(x3, cells, wts, valid, rmax, rse, cmax, cse, lse, term)
+        C.densece_reduce(term, valid, out)
+        ctx.save_for_backward(x3, cells, wts, lse, out)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x3, cells, wts, lse, out = ctx.saved_tensors
+        gx = torch.empty_like(x3)
+        _ext.ext().densece_bwd(x3, cells, wts, lse, out, gx, g.float().contiguous().reshape(1))
+        return gx, None, None
+
+
+def warp_loss_from_corr(corr4d: torch.Tensor, batch) -> torch.Tensor:
+    """Dense correspondence loss (ops/reference.py dense_ce) of a
+    [B,1,hA,wA,hB,wB] volume whose two views are warps of one image, against
+    the batch's ``warp_maps`` [B, 2, 12] fp64 (data/augment.py view_maps).  The
+    maps are used as they are when they already are contiguous fp64 on the
+    volume's device (the trainer moves the batch once)."""
+    if "warp_maps" not in batch:
+        raise KeyError("warp loss: the batch has no 'warp_maps' (use the two-view input path, gpu_view_batch)")
+    if corr4d.dim() != 6 or corr4d.shape[1] != 1:
+        raise ValueError(f"warp loss: expected a [B,1,hA,wA,hB,wB] volume, got {tuple(corr4d.shape)}")
+    maps = batch["warp_maps"]
+    b = corr4d.shape[0]
+    if maps.dim() != 3 or tuple(maps.shape) != (b, 2, 12):
+        raise ValueError(f"warp loss: warp_maps must be [{b}, 2, 12], got {tuple(maps.shape)}")
+    if _ext.use_hip(corr4d):
+        ha, wa, hb, wb = corr4d.shape[2:]
+        maps = maps.to(device=corr4d.device, dtype=torch.float64).contiguous()
+        _ext.count("densece")
+        return DenseCEFn.apply(corr4d.reshape(b, ha * wa, hb * wb), maps, (ha, wa, hb, wb))
+    return ref.dense_ce(corr4d, maps)
 
 
 def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> torch.Tensor:

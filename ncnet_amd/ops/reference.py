@@ -268,6 +268,100 @@ def keypoint_ce_grad(corr4d: torch.Tensor, source_points: torch.Tensor, target_p
     return (g / (2 * valid.sum().clamp(min=1))).reshape(corr4d.shape)
 
 
+def _unit_axis(q: torch.Tensor, n: int):
+    """Cells i0, i1 and fraction f of unit coordinates ``q`` on an n-cell axis:
+    ``_keypoint_axis`` on unit coordinates (normalised = 2 unit - 1)."""
+    u = (q * (n - 1)).clamp(0, n - 1)
+    i0 = u.floor().clamp(max=max(n - 2, 0)).long()
+    i1 = (i0 + 1).clamp(max=n - 1)
+    return i0, i1, u - i0.to(u.dtype)
+
+
+def _dense_side(m: torch.Tensor, h: int, w: int, gh: int, gw: int):
+    """One side of ``dense_targets``: ``m`` [B, 12] fp64, this side's grid
+    h x w, the other grid gh x gw -> cells [B, h*w, 4], weights, valid."""
+    i, j = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    ux = (j / (w - 1) if w > 1 else torch.zeros_like(j)).reshape(1, -1)
+    uy = (i / (h - 1) if h > 1 else torch.zeros_like(i)).reshape(1, -1)
+    c = lambda k: m[:, k].unsqueeze(1)  # noqa: E731
+    qx, qy = c(0) * ux + c(1) * uy + c(2), c(3) * ux + c(4) * uy + c(5)
+    sx, sy = c(6) * ux + c(7) * uy + c(8), c(9) * ux + c(10) * uy + c(11)
+    valid = (qx >= 0) & (qx <= 1) & (qy >= 0) & (qy <= 1) & (sx >= 0) & (sx <= 1) & (sy >= 0) & (sy <= 1)
+    # an invalid cell has no target (zero cells and weights); this also keeps a non-finite map out of the clamp
+    i0, i1, fi = _unit_axis(torch.where(valid, qy, torch.zeros_like(qy)), gh)
+    j0, j1, fj = _unit_axis(torch.where(valid, qx, torch.zeros_like(qx)), gw)
+    cells = torch.stack((i0 * gw + j0, i0 * gw + j1, i1 * gw + j0, i1 * gw + j1), 2)
+    wts = torch.stack(((1 - fi) * (1 - fj), (1 - fi) * fj, fi * (1 - fj), fi * fj), 2)
+    keep = valid.unsqueeze(2)
+    return cells * keep, wts * keep, valid
+
+
+def dense_targets(warp_maps: torch.Tensor, hA: int, wA: int, hB: int, wB: int):
+    """The target table of ``dense_ce`` in fp64 (the oracle of csrc/densece.hip
+    ``densece_table`` and the CPU path).
+
+    ``warp_maps`` [B, 2, 12]: row [b, 0] describes the A cells, [b, 1] the B
+    cells; a row holds two affine maps (m00, m01, c0, m10, m11, c1) on unit
+    coordinates (ux, uy) of its view (pixel / (extent - 1)): entries 0..5 into
+    the other view's unit frame, 6..11 into the source image's.  Cell (i, j) of
+    an h x w grid sits at (j / (w - 1), i / (h - 1)) (0 on an axis of length
+    1).  A cell is valid when both images of it lie in [0, 1]^2; its target
+    position q takes, per axis of n cells, u = clamp(q (n - 1), 0, n - 1),
+    i0 = min(floor(u), max(n - 2, 0)), i1 = min(i0 + 1, n - 1), f = u - i0
+    (``_keypoint_axis``), and the four cells / bilinear weights of
+    ``keypoint_weight_maps``.  Returns ``(cells_a [B, R, 4] (of the B grid),
+    wts_a [B, R, 4], valid_a [B, R], cells_b [B, C, 4] (of the A grid), wts_b,
+    valid_b)``; invalid cells carry zero cells and weights."""
+    m = warp_maps.detach().to(device="cpu", dtype=torch.float64)
+    if m.dim() != 3 or m.shape[1:] != (2, 12):
+        raise ValueError(f"warp_maps must be [B, 2, 12], got {tuple(warp_maps.shape)}")
+    return _dense_side(m[:, 0], hA, wA, hB, wB) + _dense_side(m[:, 1], hB, wB, hA, wA)
+
+
+def _dense_maps(corr4d, warp_maps):
+    """x [B, R, C] and the dense weight maps V [B, R, C] (rows of valid A
+    cells), U [B, R, C] (columns of valid B cells), N_A, N_B."""
+    if corr4d.dim() != 6 or corr4d.shape[1] != 1:
+        raise ValueError(f"dense_ce: expected a [B,1,hA,wA,hB,wB] volume, got {tuple(corr4d.shape)}")
+    b, _, ha, wa, hb, wb = corr4d.shape
+    dt, dev = corr4d.dtype, corr4d.device
+    ca, va, oka, cb, vb, okb = dense_targets(warp_maps, ha, wa, hb, wb)
+    R, C = ha * wa, hb * wb
+    V = torch.zeros(b, R, C, dtype=torch.float64).scatter_add_(2, ca, va)             # coinciding cells add up
+    U = torch.zeros(b, C, R, dtype=torch.float64).scatter_add_(2, cb, vb).transpose(1, 2)
+    n_a, n_b = int(oka.sum()), int(okb.sum())
+    return (corr4d.reshape(b, R, C), V.to(device=dev, dtype=dt), U.to(device=dev, dtype=dt),
+            oka.to(dev), okb.to(dev), max(1, n_a), max(1, n_b))
+
+
+def dense_ce(corr4d: torch.Tensor, warp_maps: torch.Tensor) -> torch.Tensor:
+    """Dense correspondence cross-entropy of a [B,1,hA,wA,hB,wB] volume whose
+    two views are affine warps of one image (an extension beyond the reference;
+    the contract of csrc/densece.hip).  With ``dense_targets``' V_r the weights
+    of valid A cell r on the B grid, U_m those of valid B cell m on the A grid
+    and x = corr4d.view(B, R, C):
+
+        L_A = -sum_{valid r} sum_m V_r(m) log_softmax(x[r, :])[m]
+        L_B = -sum_{valid m} sum_r U_m(r) log_softmax(x[:, m])[r]
+        loss = (L_A / max(1, N_A) + L_B / max(1, N_B)) / 2
+
+    N_A, N_B: the valid cells over the batch.  A batch without a valid cell
+    gives 0 (and a zero gradient)."""
+    x, V, U, _, _, n_a, n_b = _dense_maps(corr4d, warp_maps)
+    l_a = -(V * torch.log_softmax(x, dim=2)).sum()
+    l_b = -(U * torch.log_softmax(x, dim=1)).sum()
+    return (l_a / n_a + l_b / n_b) / 2
+
+
+def dense_ce_grad(corr4d: torch.Tensor, warp_maps: torch.Tensor) -> torch.Tensor:
+    """Closed-form d dense_ce / d corr4d (what the HIP backward evaluates):
+    validA_r (softmax(x[r, :])[m] - V_r(m)) / (2 N_A) + validB_m (softmax(x[:, m])[r] - U_m(r)) / (2 N_B)."""
+    x, V, U, oka, okb, n_a, n_b = _dense_maps(corr4d, warp_maps)
+    ga = (torch.softmax(x, dim=2) - V) * oka.unsqueeze(2).to(x.dtype)
+    gb = (torch.softmax(x, dim=1) - U) * okb.unsqueeze(1).to(x.dtype)
+    return (ga / (2 * n_a) + gb / (2 * n_b)).reshape(corr4d.shape)
+
+
 def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> torch.Tensor:
     """mean(scores_A + scores_B) / 2 (train.py:134); needs square maps like the
     reference (train.py:124) only when the two score vectors differ in length,

@@ -15,6 +15,17 @@ Same flags and defaults as the reference, plus:
                        --synthetic N (synthetic pairs with known keypoints) or
                        --train_pairs_csv / --val_pairs_csv (test_pairs.csv
                        layout); every validation epoch also reports PCK@0.1
+  --loss warp          warp-supervised training from plain images, no annotation:
+                       every image gives two random views (--aug_* set the
+                       ranges) whose dense correspondence is a closed-form affine
+                       map; the loss is the dense cross-entropy of
+                       ops/reference.py dense_ce (csrc/densece.hip).  Images: the
+                       distinct names of train_pairs.csv / val_pairs.csv under
+                       --dataset_csv_path, or --image_dir DIR, or --synthetic N.
+                       Implies the uint8 input path; validation draws the same
+                       views every epoch and reports PCK@0.1 of a 25 x 25 grid
+  --image_dir DIR      --loss warp: all .jpg / .jpeg / .png under DIR, sorted; the
+                       last tenth (at least one image) is the validation set
   --gpu_input          --loss strong with --train_pairs_csv / --val_pairs_csv:
                        the workers only decode; one uint8 copy and one HIP
                        launch resize + normalise the batch on the GPU (what
@@ -64,10 +75,11 @@ from torch.utils.data import DataLoader, Subset
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from ncnet_amd.data import (ImagePairDataset, NormalizeImageDict, PFPascalDataset,  # noqa: E402
-                            SyntheticCorrespondenceDataset, SyntheticPairDataset)
+from ncnet_amd.data import (ImagePairDataset, NormalizeImageDict, PFPascalDataset, SingleImageDataset,  # noqa: E402
+                            SyntheticCorrespondenceDataset, SyntheticImageDataset, SyntheticPairDataset)
 from ncnet_amd.data.augment import PairAugment  # noqa: E402
-from ncnet_amd.data.datasets import collate_uint8_pairs, gpu_pair_batch  # noqa: E402
+from ncnet_amd.data.datasets import (collate_uint8_images, collate_uint8_pairs, gpu_pair_batch,  # noqa: E402
+                                     gpu_view_batch)
 from ncnet_amd.engine.checkpoint import capture_rng, load_checkpoint, restore_rng, save_checkpoint  # noqa: E402
 from ncnet_amd.engine.trainer import AsyncLossLog, Trainer, make_adam  # noqa: E402
 from ncnet_amd.models import ImMatchNet  # noqa: E402
@@ -110,10 +122,15 @@ def build_parser():
                         "and backward (fp32-class forward numerics at ~1/3 less NC cost than fp32). Over 24 seeds "
                         "bf16, mixed and fp32 took off at the same rate (profiles/r5/ablation): there is no evidence "
                         "that either learns where bf16 does not; pick them for forward numerics, not for learning")
-    p.add_argument("--loss", type=str, default="weak", choices=["weak", "strong"],
+    p.add_argument("--loss", type=str, default="weak", choices=["weak", "strong", "warp"],
                    help="weak: the reference's weakly-supervised score; strong: keypoint-supervised cross-entropy "
                         "on pairs with annotated correspondences (--synthetic N, or --train_pairs_csv / "
-                        "--val_pairs_csv in the test_pairs.csv layout)")
+                        "--val_pairs_csv in the test_pairs.csv layout); warp: dense cross-entropy on two random views "
+                        "of every image (the images of train_pairs.csv / val_pairs.csv, --image_dir DIR or "
+                        "--synthetic N; the --aug_* flags set the view ranges)")
+    p.add_argument("--image_dir", type=str, default="",
+                   help="--loss warp: train on all .jpg / .jpeg / .png under DIR (sorted; the last tenth, at least "
+                        "one image, is the validation set)")
     p.add_argument("--train_pairs_csv", type=str, default="",
                    help="--loss strong: training pairs with keypoints (source,target,class,XA,YA,XB,YB)")
     p.add_argument("--val_pairs_csv", type=str, default="", help="--loss strong: validation pairs with keypoints")
@@ -143,6 +160,25 @@ def build_parser():
     return p
 
 
+def warp_image_sets(args):
+    """--loss warp: (image root, training names, validation names)."""
+    if args.image_dir:
+        names = sorted(os.path.relpath(os.path.join(d, f), args.image_dir)
+                       for d, _, files in os.walk(args.image_dir) for f in files
+                       if f.lower().endswith((".jpg", ".jpeg", ".png")))
+        n_val = max(1, len(names) // 10)
+        if len(names) < 2:
+            raise SystemExit(f"--image_dir {args.image_dir}: found {len(names)} .jpg / .jpeg / .png images, need at "
+                             "least 2 (one to train on, one to validate on)")
+        return args.image_dir, names[:-n_val], names[-n_val:]
+    import pandas as pd
+    out = []
+    for fn in ("train_pairs.csv", "val_pairs.csv"):
+        data = pd.read_csv(os.path.join(args.dataset_csv_path, fn))
+        out.append(sorted(set(data.iloc[:, 0].tolist()) | set(data.iloc[:, 1].tolist())))
+    return args.dataset_image_path, out[0], out[1]
+
+
 def augment_seed(seed: int, rank: int, first_epoch: int) -> int:
     """Seed of a process's augmentation generator: a mix of (--seed, rank, first
     epoch) reduced into the range torch.Generator.manual_seed takes, for any
@@ -170,21 +206,27 @@ class _Shard(torch.utils.data.Sampler):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     strong = args.loss == "strong"
+    warp = args.loss == "warp"
+    if warp and args.cpu_resize:
+        raise SystemExit("--loss warp cuts both views of an image from its decoded uint8 pixels on the device (the "
+                         "uint8 input path); --cpu_resize, which resizes in the workers, cannot be combined with it")
+    if args.image_dir and not warp:
+        raise SystemExit("--image_dir is the image source of --loss warp")
     if strong and not args.synthetic and not (args.train_pairs_csv and args.val_pairs_csv):
         raise SystemExit("--loss strong needs pairs with keypoints: give --synthetic N, or --train_pairs_csv and "
                          "--val_pairs_csv (test_pairs.csv layout: source,target,class,XA,YA,XB,YB); "
                          "the shipped train_pairs.csv / val_pairs.csv carry no keypoints")
     for flag in ("augment", "gpu_input"):
-        if getattr(args, flag) and (args.synthetic or args.cpu_resize):
+        if getattr(args, flag) and ((args.synthetic and not warp) or args.cpu_resize):
             raise SystemExit(f"--{flag} works on the uint8 input path (decoded image files, resized on the device); "
                              f"--{'synthetic' if args.synthetic else 'cpu_resize'} batches carry float images")
     augment = None
-    if args.augment:
+    if args.augment or warp:                       # --loss warp: the ranges of the two views
         try:
             augment = PairAugment(rot_deg=args.aug_rot_deg, scale=tuple(args.aug_scale), shift=args.aug_shift,
                                   flip=args.aug_flip, gain=tuple(args.aug_gain), bias=args.aug_bias)
         except ValueError as e:
-            raise SystemExit(f"--augment: {e}")
+            raise SystemExit(f"--{'augment' if args.augment else 'loss warp'}: {e}")
     ctx = init_distributed()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -216,7 +258,15 @@ def main(argv=None):
     size = (args.image_size, args.image_size)
     uint8_input = args.gpu_input or args.augment       # asked for: on any device (CPU: the torch fallback)
     gpu_resize = (ctx.device.type == "cuda" and not args.cpu_resize) or uint8_input
-    if strong:
+    if warp:
+        gpu_resize = True
+        if args.synthetic:
+            train_set = SyntheticImageDataset(args.synthetic, size, seed=1)
+            test_set = SyntheticImageDataset(max(2 * args.batch_size, args.synthetic // 8), size, seed=2)
+        else:
+            root, tr_names, va_names = warp_image_sets(args)
+            train_set, test_set = SingleImageDataset(root, tr_names), SingleImageDataset(root, va_names)
+    elif strong:
         # keypoint datasets yield float images unless the uint8 path is asked for
         gpu_resize = uint8_input
         if args.synthetic:
@@ -245,12 +295,19 @@ def main(argv=None):
     if nw < 0:
         nw = min(8, max(1, (os.cpu_count() or 2) // max(1, ctx.world_size) - 1)) if pin else 0
     lkw = dict(batch_size=args.batch_size, num_workers=nw, pin_memory=pin, drop_last=True,
-               collate_fn=collate_uint8_pairs if (gpu_resize and not args.synthetic) else None,
+               collate_fn=collate_uint8_images if warp else
+               collate_uint8_pairs if (gpu_resize and not args.synthetic) else None,
                persistent_workers=nw > 0, prefetch_factor=4 if nw > 0 else None)
     train_loader = DataLoader(train_set, sampler=tr_sampler, **lkw)
     test_loader = DataLoader(test_set, sampler=te_sampler, **lkw)
     aug_rng = torch.Generator() if augment is not None else None     # seeded below, once the first epoch is known
-    if gpu_resize and not args.synthetic:
+    val_rng = torch.Generator() if warp else None    # re-seeded before every validation epoch: same views each time
+    if warp:
+        # validation batches also carry the 25 x 25 grid points, for PCK@0.1 of the same volume
+        trainer_to_device = lambda batch: gpu_view_batch(  # noqa: E731
+            batch, ctx.device, size[0], size[1], augment, aug_rng if model.training else val_rng,
+            with_points=not model.training)
+    elif gpu_resize and not args.synthetic:
         # training batches only (the Trainer sets model.training before it touches a loader): validation
         # keeps the plain resize and its points, so its loss and PCK compare with an un-augmented run
         trainer_to_device = lambda batch: gpu_pair_batch(  # noqa: E731
@@ -279,6 +336,8 @@ def main(argv=None):
             print(f"Resumed from {args.resume} at epoch {start_epoch}")
     if aug_rng is not None:
         aug_rng.manual_seed(augment_seed(args.seed, ctx.rank, start_epoch))
+    if val_rng is not None:
+        val_rng.manual_seed(augment_seed(args.seed + 7, ctx.rank, 0))
     if ctx.is_main:
         print("Checkpoint name: " + checkpoint_name)
 
@@ -360,6 +419,8 @@ def main(argv=None):
     for epoch in range(start_epoch, args.num_epochs + 1):
         tr_sampler.set_epoch(epoch)
         train_loss[epoch - 1] = trainer.process_epoch("train", epoch, train_loader, args.log_interval, args.sync_log)
+        if val_rng is not None:                        # the same validation views every epoch: loss and PCK compare
+            val_rng.manual_seed(augment_seed(args.seed + 7, ctx.rank, 0))
         test_loss[epoch - 1] = trainer.process_epoch("test", epoch, test_loader, args.log_interval, args.sync_log)
         is_best = test_loss[epoch - 1] < best_test_loss
         best_test_loss = min(test_loss[epoch - 1], best_test_loss)
