@@ -61,6 +61,9 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["bf16", "fp16", "fp32"], default="bf16",
                     help="bf16 (default), fp16 (IEEE-half features + correlation), fp32 (fp32-accurate: fp32 trunk, "
                          "bf16x3 correlation and NeighConsensus, the reference's numerics)")
+    ap.add_argument("--k_size", type=int, default=None,
+                    help="max-pool the correlation k x k x k x k before NeighConsensus (relocalization); default: the "
+                         "checkpoint's relocalization_k_size if it has one, else 0")
     args = ap.parse_args(argv)
     ctx = init_distributed()
     if ctx.is_main:
@@ -68,6 +71,14 @@ def main(argv=None):
     model = ImMatchNet(use_cuda=ctx.device.type == "cuda", checkpoint=args.checkpoint or None,
                        ncons_kernel_sizes=args.ncons_kernel_sizes, ncons_channels=args.ncons_channels,
                        dtype="fp32" if args.precision == "fp32" else "bf16", corr_dtype=args.precision).to(ctx.device)
+    k_size = args.k_size
+    if k_size is None:
+        k_size = int(getattr(model.checkpoint_args, "relocalization_k_size", 0) or 0)
+    if k_size > 1 and args.image_size % (16 * k_size):
+        raise SystemExit(f"k_size {k_size}{'' if args.k_size is not None else ' (from the checkpoint)'}: the feature "
+                         f"grid (--image_size {args.image_size} / 16 = {args.image_size / 16:g} cells) must be a "
+                         "multiple of it; pass a matching --image_size, or --k_size 0 to evaluate un-pooled")
+    model.relocalization_k_size = k_size
     model.eval()
     size = (args.image_size, args.image_size)
     if args.synthetic:
@@ -84,8 +95,12 @@ def main(argv=None):
     with torch.inference_mode():
         for i, batch in enumerate(loader):
             batch = {k: (v.to(ctx.device) if torch.is_tensor(v) else v) for k, v in batch.items()}
-            corr4d = model(batch)
-            xA, yA, xB, yB, _ = corr_to_matches(corr4d, do_softmax=True)
+            if k_size > 1:
+                corr4d, delta4d = model(batch)
+                xA, yA, xB, yB, _ = corr_to_matches(corr4d, delta4d=delta4d, k_size=k_size, do_softmax=True)
+            else:
+                corr4d = model(batch)
+                xA, yA, xB, yB, _ = corr_to_matches(corr4d, do_softmax=True)
             stats = pck_metric(batch, pos, (xA, yA, xB, yB), stats)
             pos += batch["source_image"].shape[0]
             if ctx.is_main:

@@ -414,24 +414,69 @@ void corr_gemm(Tensor A, Tensor B, Tensor C, c10::optional<Tensor> amap, c10::op
      "corr_gemm");
 }
 
+// Volume v pools A[amap[v]] . B[bmap[v]]^T (maps absent: v); val / idx have one volume per map entry.
 void corr_gemm_pool2(Tensor A, Tensor B, Tensor val, Tensor idx, int64_t hA, int64_t wA, int64_t hB, int64_t wB,
-                     double out_scale) {
+                     double out_scale, c10::optional<Tensor> amap, c10::optional<Tensor> bmap) {
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
   const bool f8 = A.scalar_type() == at::kFloat8_e4m3fn, h = A.scalar_type() == at::kHalf;
   const auto dt = f8 ? at::kFloat8_e4m3fn : h ? at::kHalf : at::kBFloat16;
   check(A, "A", dt); check(B, "B", dt);
   check(val, "val", at::kFloat); check(idx, "idx", at::kByte);
   TORCH_CHECK(!f8 || A.size(2) % 16 == 0, "fp8 K must be a multiple of 16");
-  TORCH_CHECK(A.dim() == 3 && B.dim() == 3 && A.size(0) == B.size(0));
+  TORCH_CHECK(A.dim() == 3 && B.dim() == 3);
   TORCH_CHECK(A.size(1) == hA * wA && B.size(1) == hB * wB && A.size(2) == B.size(2));
   TORCH_CHECK(hA % 2 == 0 && wA % 2 == 0 && hB % 2 == 0 && wB % 2 == 0, "pooling needs even feature sizes");
   TORCH_CHECK(A.size(2) % 8 == 0);
-  check_shape(val, "val", {A.size(0), hA / 2, wA / 2, hB / 2, wB / 2});
-  check_shape(idx, "idx", {A.size(0), hA / 2, wA / 2, hB / 2, wB / 2});
-  ok(ncnet_corr_gemm_pool2(A.data_ptr(), B.data_ptr(), (float*)val.data_ptr(), (uint8_t*)idx.data_ptr(), A.size(0), hA,
-                           wA, hB, wB, A.size(2), A.size(1) * A.size(2), B.size(1) * B.size(2),
-                           f8 ? (float)out_scale : 0.f, h ? 1 : 0, cur_stream(A)),
+  TORCH_CHECK(val.dim() == 5, "val must be [V, hA/2, wA/2, hB/2, wB/2]");
+  const int64_t batch = val.size(0);
+  if (amap.has_value()) {
+    // as corr_gemm: built from arange / roll by ncnet_amd.ops.correlation (in range by
+    // construction); no device->host read here, the call stays async
+    check(*amap, "amap", at::kInt); check_shape(*amap, "amap", {batch});
+  } else TORCH_CHECK(A.size(0) == batch);
+  if (bmap.has_value()) {
+    check(*bmap, "bmap", at::kInt); check_shape(*bmap, "bmap", {batch});
+  } else TORCH_CHECK(B.size(0) == batch);
+  check_shape(val, "val", {batch, hA / 2, wA / 2, hB / 2, wB / 2});
+  check_shape(idx, "idx", {batch, hA / 2, wA / 2, hB / 2, wB / 2});
+  ok(ncnet_corr_gemm_pool2(A.data_ptr(), B.data_ptr(), (float*)val.data_ptr(), (uint8_t*)idx.data_ptr(),
+                           opt_ptr<int>(amap), opt_ptr<int>(bmap), batch, hA, wA, hB, wB, A.size(2),
+                           A.size(1) * A.size(2), B.size(1) * B.size(2), f8 ? (float)out_scale : 0.f, h ? 1 : 0,
+                           cur_stream(A)),
      "corr_gemm_pool2");
+}
+
+// One direction (dir 0: gA, dir 1: gB) of the feature gradient of corr_gemm_pool2, rows in
+// 2x2-block order.  ft bf16 [nother, K, ldr]: the other side's features transposed and zero
+// padded to ldr % 32 == 0; g fp32 / code uint8 [V, hA/2, wA/2, hB/2, wB/2]; off [nout + 1],
+// vol [V], omap [V] int32 (the output images' volume lists and each volume's other-side image,
+// built and validated on the host by ncnet_amd.ops.correlation); out fp32 [nout, rows, K].
+void corr_pool2_bwd(Tensor ft, Tensor g, Tensor code, Tensor off, Tensor vol, Tensor omap, Tensor out, int64_t dir,
+                    int64_t hA, int64_t wA, int64_t hB, int64_t wB) {
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(ft.device());
+  check(ft, "ft", at::kBFloat16); check(g, "g", at::kFloat); check(code, "code", at::kByte);
+  check(off, "off", at::kInt); check(vol, "vol", at::kInt); check(omap, "omap", at::kInt);
+  check(out, "out", at::kFloat);
+  TORCH_CHECK(dir == 0 || dir == 1, "dir must be 0 (gA) or 1 (gB)");
+  TORCH_CHECK(hA > 0 && wA > 0 && hB > 0 && wB > 0 && hA % 2 == 0 && wA % 2 == 0 && hB % 2 == 0 && wB % 2 == 0,
+              "pooling needs even feature sizes");
+  TORCH_CHECK(ft.dim() == 3 && out.dim() == 3 && g.dim() == 5);
+  const int64_t V = g.size(0), nout = out.size(0), nother = ft.size(0), K = ft.size(1), ldr = ft.size(2);
+  const int64_t rows = dir == 0 ? hA * wA : hB * wB, red = dir == 0 ? hB * wB : hA * wA;
+  TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16");
+  TORCH_CHECK(ldr % 32 == 0 && ldr >= red, "ft rows must be padded to a multiple of 32");
+  check_shape(g, "g", {V, hA / 2, wA / 2, hB / 2, wB / 2});
+  check_shape(code, "code", {V, hA / 2, wA / 2, hB / 2, wB / 2});
+  check_shape(out, "out", {nout, rows, K});
+  check_shape(off, "off", {nout + 1}); check_shape(vol, "vol", {V}); check_shape(omap, "omap", {V});
+  TORCH_CHECK(nother * K * ldr < (1LL << 40) && V * rows * red < (1LL << 40));
+  TORCH_CHECK(((uintptr_t)ft.data_ptr() & 15) == 0 && ((uintptr_t)out.data_ptr() & 15) == 0,
+              "corr_pool2_bwd: ft and out must start 16-byte aligned");
+  ok(ncnet_corr_pool2_bwd(ft.data_ptr(), (const float*)g.data_ptr(), (const uint8_t*)code.data_ptr(),
+                          (const int*)off.data_ptr(), (const int*)vol.data_ptr(), (const int*)omap.data_ptr(),
+                          (float*)out.data_ptr(), (int)V, (int)nout, (int)nother, (int)dir, (int)hA, (int)wA, (int)hB,
+                          (int)wB, (int)K, (int)ldr, cur_stream(ft)),
+     "corr_pool2_bwd");
 }
 
 // x [V,R,C] fp32 -> per-row (dim 2) stats [V,R]: max, first argmax, and se =
@@ -1306,7 +1351,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2norm_rows", &l2norm_rows);
   m.def("l2norm_rows_bwd", &l2norm_rows_bwd);
   m.def("corr_gemm", &corr_gemm);
-  m.def("corr_gemm_pool2", &corr_gemm_pool2);
+  m.def("corr_gemm_pool2", &corr_gemm_pool2, py::arg("A"), py::arg("B"), py::arg("val"), py::arg("idx"), py::arg("hA"),
+        py::arg("wA"), py::arg("hB"), py::arg("wB"), py::arg("out_scale"), py::arg("amap") = py::none(),
+        py::arg("bmap") = py::none());
+  m.def("corr_pool2_bwd", &corr_pool2_bwd);
   m.def("stats_rows", &stats_rows);
   m.def("stats_cols", &stats_cols);
   m.def("stats2d", &stats2d);

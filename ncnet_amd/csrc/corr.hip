@@ -682,14 +682,14 @@ extern "C" int ncnet_corr_gemm(const void* A, const void* B, void* C, const int*
 }
 
 // The same selection with the POOL epilogue (fp32 pooled values + codes only).
-extern "C" int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_val, uint8_t* pool_idx, int batch,
-                                     int hA, int wA, int hB, int wB, int K, long long sA, long long sB,
-                                     float fp8_out_scale, int f16, hipStream_t stream) {
+extern "C" int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_val, uint8_t* pool_idx, const int* amap,
+                                     const int* bmap, int batch, int hA, int wA, int hB, int wB, int K, long long sA,
+                                     long long sB, float fp8_out_scale, int f16, hipStream_t stream) {
   const bool f8 = fp8_out_scale != 0.f;
   if (f8 && f16) return -1;
   if (K % (f8 ? 16 : 8) != 0 || (hA & 1) || (wA & 1) || (hB & 1) || (wB & 1)) return -1;
   GemmArgs p{};
-  p.A = A; p.B = B; p.C = nullptr;
+  p.A = A; p.B = B; p.C = nullptr; p.amap = amap; p.bmap = bmap;
   p.M = hA * wA; p.N = hB * wB; p.K = K; p.sA = sA; p.sB = sB;
   p.out_scale = fp8_out_scale;
   p.pool_ks = 2; p.pool_val = pool_val; p.pool_idx = pool_idx;

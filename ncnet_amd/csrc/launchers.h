@@ -178,10 +178,29 @@ int ncnet_corr_gemm(const void* A, const void* B, void* C, const int* amap, cons
                     int K, long long sA, long long sB, long long sC, int out_bf16, float fp8_out_scale, int f16,
                     hipStream_t stream);
 // Fused correlation + 2x2x2x2 max-pool.  A rows / B rows must be in
-// 2x2-block order; hA, wA, hB, wB even.
-int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_val, uint8_t* pool_idx, int batch, int hA, int wA,
-                          int hB, int wB, int K, long long sA, long long sB, float fp8_out_scale, int f16,
-                          hipStream_t stream);
+// 2x2-block order; hA, wA, hB, wB even.  Volume b pools A[amap[b]] . B[bmap[b]]^T
+// (maps null: b); batch = the number of volumes.
+int ncnet_corr_gemm_pool2(const void* A, const void* B, float* pool_val, uint8_t* pool_idx, const int* amap,
+                          const int* bmap, int batch, int hA, int wA, int hB, int wB, int K, long long sA, long long sB,
+                          float fp8_out_scale, int f16, hipStream_t stream);
+
+// ---- backward of the pooled correlation (csrc/corrpool_bwd.hip) -----------
+// One direction of the feature gradient of ncnet_corr_gemm_pool2; rows in 2x2-block
+// order, M = hA wA, N = hB wB, g fp32 / code uint8 [V, M/4, N/4] (code as the pool
+// writes it; only the low bit of each 2-bit field is read).
+//   dir 0: out[n][4I + a] = sum g[v,I,J] * fb[omap[v]][4J + b] over J and the volumes of image n,
+//   dir 1: out[n][4J + b] = sum g[v,I,J] * fa[omap[v]][4I + a] over I and the volumes of image n,
+// out fp32 [nout, M (dir 0) or N (dir 1), K], every element written once (zeros for an
+// image without volumes), fixed summation order.  ft: the OTHER side's features
+// transposed, bf16 [nother, K, ldr], ldr % 32 == 0 and >= that side's rows, zero
+// past them.  g enters the MFMA rounded to bf16.  Volumes of output image n:
+// vol[off[n] .. off[n + 1]) (off [nout + 1], vol [V], device int32, built and
+// validated on the host); omap [V]: each volume's image on the other side.  An
+// out-of-range list entry is skipped, never dereferenced.  K % 16 == 0 and ft, out
+// 16-byte aligned (else -3).
+int ncnet_corr_pool2_bwd(const void* ft, const float* g, const uint8_t* code, const int* off, const int* vol,
+                         const int* omap, float* out, int V, int nout, int nother, int dir, int hA, int wA, int hB,
+                         int wB, int K, int ldr, hipStream_t stream);
 
 // ---- correlation-volume ops (csrc/volume.hip) -----------------------------
 // x [rows, C] fp32 -> per-row max, first argmax (arg or null) and se (or null):

@@ -120,12 +120,21 @@ def strong_loss(model, batch) -> torch.Tensor:
     return strong_loss_from_corr(_positive_volumes(model, batch), batch)
 
 
-def _positive_volumes(model, batch) -> torch.Tensor:
-    """The positive pairs' volumes [B,1,h,w,h,w] of a batch (backbone included)."""
+def _positive_volumes(model, batch, return_delta: bool = False):
+    """The positive pairs' volumes [B,1,h,w,h,w] of a batch (backbone included);
+    ``return_delta``: also the relocalization pool's offsets (None without one)."""
     src, tgt = batch["source_image"], batch["target_image"]
     with segment("backbone"):
         f, hw = model.extract(torch.cat((src, tgt), 0))
+    if return_delta:
+        return model.match_volumes_from_features(f, hw, src.shape[0], return_delta=True)
     return model.match_volumes_from_features(f, hw, src.shape[0])
+
+
+def _reloc_k(model) -> int:
+    """The model's relocalization pool size when it pools (k > 1), else 1."""
+    k = int(getattr(model, "relocalization_k_size", 0) or 0)
+    return k if k > 1 else 1
 
 
 def strong_loss_from_features(model, feats, batch) -> torch.Tensor:
@@ -151,13 +160,18 @@ _KEYPOINT_FIELDS = ("source_points", "target_points", "source_im_size", "target_
 _WARP_FIELDS = ("warp_maps",) + _KEYPOINT_FIELDS
 
 
-def batch_pck(corr4d, batch, alpha: float = 0.1) -> torch.Tensor:
+def batch_pck(corr4d, batch, alpha: float = 0.1, delta4d=None, k_size: int = 1) -> torch.Tensor:
     """Per-sample PCK@alpha [B] of a volume, by the evaluation's own path
     (eval_pf_pascal.py: corr_to_matches with softmax, then pck_metric's
-    bilinear keypoint transfer); NaN for a sample without keypoints."""
+    bilinear keypoint transfer); NaN for a sample without keypoints.
+    ``delta4d`` / ``k_size``: the relocalization pool's offsets and size, so the
+    matches land on the full-resolution grid."""
     from ..eval.pck import pck
     from ..eval.point_tnf import PointsToPixelCoords, PointsToUnitCoords, bilinearInterpPointTnf, corr_to_matches
-    xA, yA, xB, yB, _ = corr_to_matches(corr4d.float(), do_softmax=True)
+    if delta4d is None:
+        xA, yA, xB, yB, _ = corr_to_matches(corr4d.float(), do_softmax=True)
+    else:
+        xA, yA, xB, yB, _ = corr_to_matches(corr4d.float(), delta4d=delta4d, k_size=k_size, do_softmax=True)
     tp_norm = PointsToUnitCoords(batch["target_points"], batch["target_im_size"])
     warped = PointsToPixelCoords(bilinearInterpPointTnf((xA, yA, xB, yB), tp_norm), batch["source_im_size"])
     return pck(batch["source_points"], warped, batch["L_pck"].view(-1).to(warped.dtype), alpha)
@@ -184,12 +198,14 @@ class TrunkPrefetcher:
         dev = next(model.parameters()).device
         fe_trainable = any(p.requires_grad for p in model.FeatureExtraction.parameters())
         self.enabled = dev.type == "cuda" and not fe_trainable and _config.RUNTIME.trunk_prefetch
+        self.fe_trainable = fe_trainable
         self.stream = torch.cuda.Stream(device=dev) if self.enabled else None
         self._pending = None
 
     def _extract(self, batch):
         src, tgt = batch["source_image"], batch["target_image"]
-        with torch.no_grad():
+        # a trainable trunk runs under the caller's autograd mode: the step's gradient has to reach it
+        with torch.set_grad_enabled(self.fe_trainable and torch.is_grad_enabled()):
             f, hw = self.model.extract(torch.cat((src, tgt), 0))
         return f, hw, src.shape[0]
 
@@ -351,15 +367,18 @@ class Trainer:
             for v in batch.values():
                 if torch.is_tensor(v) and v.is_cuda:
                     v.record_stream(main)
+        k = _reloc_k(self.model)
         if self.loss == "strong":
-            vol = _positive_volumes(self.model, batch)
+            vol, delta = _positive_volumes(self.model, batch, return_delta=True) if k > 1 else \
+                (_positive_volumes(self.model, batch), None)
             if "L_pck" in batch:              # PCK of the same volume, summarised per epoch by process_epoch
-                self._pck.append(batch_pck(vol, batch))
+                self._pck.append(batch_pck(vol, batch, delta4d=delta, k_size=k))
             return strong_loss_from_corr(vol, batch).detach()
         if self.loss == "warp":
-            vol = _positive_volumes(self.model, batch)
+            vol, delta = _positive_volumes(self.model, batch, return_delta=True) if k > 1 else \
+                (_positive_volumes(self.model, batch), None)
             if "L_pck" in batch and "source_points" in batch:
-                self._pck.append(batch_pck(vol, batch))
+                self._pck.append(batch_pck(vol, batch, delta4d=delta, k_size=k))
             return warp_loss_from_corr(vol, batch).detach()
         return weak_loss(self.model, batch, self.normalization).detach()
 

@@ -26,8 +26,8 @@ import torch.nn.functional as F
 
 from ..ops import reference as ref
 from ..ops.conv4d import Conv4d
-from ..ops.correlation import (correlation, correlation_pool2, correlation_x3, l2norm_pack, l2norm_pack_f16,
-                               l2norm_pack_fp8, l2norm_pack_split, maxpool4d as _maxpool4d)
+from ..ops.correlation import (_device_map, correlation, correlation_pool2, correlation_x3, l2norm_pack,
+                               l2norm_pack_f16, l2norm_pack_fp8, l2norm_pack_split, maxpool4d as _maxpool4d)
 from ..ops import _ext as _ext_mod
 from ..ops.mutual import (mutual_matching, mutual_matching_nc_input as _mm_nc_input,
                           mutual_matching_padded as _mm_padded)
@@ -220,6 +220,13 @@ def _pair_maps(b: int, device):
     return m
 
 
+def _pair_map_lists(b: int):
+    """``_pair_maps`` as host int tuples (the pooled correlation's backward
+    builds its per-image volume lists from them on the host)."""
+    ar = tuple(range(b))
+    return ar + ar[1:] + ar[:1], ar + ar
+
+
 class ImMatchNet(nn.Module):
     def __init__(self, feature_extraction_cnn: str = "resnet101", feature_extraction_last_layer: str = "",
                  feature_extraction_model_file: str | None = None, return_correlation: bool = False,
@@ -235,6 +242,9 @@ class ImMatchNet(nn.Module):
             if args is not None:
                 ncons_channels = getattr(args, "ncons_channels", ncons_channels)
                 ncons_kernel_sizes = getattr(args, "ncons_kernel_sizes", ncons_kernel_sizes)
+        # the training run's argparse namespace, if the checkpoint has one (eval_pf_pascal.py
+        # reads its relocalization_k_size)
+        self.checkpoint_args = ck.get("args") if ck is not None else None
         self.use_cuda = use_cuda and torch.cuda.is_available()
         self.normalize_features = normalize_features
         self.return_correlation = return_correlation
@@ -415,11 +425,47 @@ class ImMatchNet(nn.Module):
             return corr4d, delta
         return corr4d
 
-    def match_volumes_from_features(self, f: torch.Tensor, hw, b: int) -> torch.Tensor:
+    def _relocalized_volumes(self, f, hw, b: int, amap, bmap):
+        """Pooled training volumes (``relocalization_k_size`` > 1) of the pairs
+        (source amap[v], target bmap[v]) -- host int tuples, None: pair v = (v, v) -- from ``f`` =
+        extract() of [source; target]: (pooled [V,1,h/k,w/k,h/k,w/k], offsets).
+        k = 2 on even grids with bf16 operands is the fused mapped pool (with its
+        HIP backward when the trunk trains); split (hi, lo) operands pool the
+        bf16x3 volume; any other k, or odd grids, pool the full volume -- frozen
+        trunk only (the unfused pool has no backward)."""
+        h, w = hw
+        k = self.relocalization_k_size
+        V = len(amap) if amap is not None else b
+        dev = (f[0] if isinstance(f, tuple) else f).device
+        # device copies for the un-fused routes (None: the identity, the positive pairs)
+        am = _device_map(amap, dev) if amap is not None else None
+        bm = _device_map(bmap, dev) if bmap is not None else None
+        if isinstance(f, tuple):               # split operands: the trunk is frozen (extract)
+            if _nc_ops.x3_dropped("corr"):
+                f = (f[0], torch.zeros_like(f[1]))
+            corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]), am, bm)
+            return _maxpool4d(corr.view(V, 1, h, w, h, w), k)
+        fa, fb = f[:b], f[b:]
+        if k == 2 and h % 2 == 0 and w % 2 == 0:
+            return correlation_pool2(fa, fb, h, w, h, w, amap=amap, bmap=bmap)
+        if torch.is_grad_enabled() and f.requires_grad:
+            raise ValueError(f"relocalization_k_size={k} on a {h} x {w} feature grid has no backward into a "
+                             "trainable trunk: training through the pooled correlation needs k = 2 and even grids")
+        return _maxpool4d(correlation(fa, fb, am, bm).view(V, 1, h, w, h, w), k)
+
+    def match_volumes_from_features(self, f: torch.Tensor, hw, b: int, return_delta: bool = False):
         """The positive volumes [B,1,h,w,h,w] alone, from ``f`` = extract() of
         the 2B images [source; target] (the keypoint-supervised loss: no rolled
-        negatives, so the NC stack runs on half the volumes of a weak step)."""
+        negatives, so the NC stack runs on half the volumes of a weak step).
+        With ``relocalization_k_size`` k > 1 the volumes are max-pooled k x k x k x k
+        before the NC stack ([B,1,h/k,..]); ``return_delta``: also the pool's
+        offsets (``None`` without pooling), as ``match_features``."""
         h, w = hw
+        if self.relocalization_k_size > 1:
+            with segment("correlation"):
+                corr, delta = self._relocalized_volumes(f, hw, b, None, None)
+            corr = self.process_correlation(corr)
+            return (corr, delta) if return_delta else corr
         with segment("correlation"):
             if isinstance(f, tuple):           # split operands (nc_precision / corr_dtype 'fp32')
                 if _nc_ops.x3_dropped("corr"):
@@ -427,7 +473,8 @@ class ImMatchNet(nn.Module):
                 corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]))
             else:
                 corr = correlation(f[:b], f[b:])
-        return self.process_correlation(corr.view(b, 1, h, w, h, w))
+        corr = self.process_correlation(corr.view(b, 1, h, w, h, w))
+        return (corr, None) if return_delta else corr
 
     def weak_loss_volumes(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
         """Positive and rolled-negative volumes [2B,1,h,w,h,w] for the weak loss.
@@ -441,11 +488,22 @@ class ImMatchNet(nn.Module):
             f, hw = self.extract(torch.cat((src, tgt), 0))
         return self.weak_loss_volumes_from_features(f, hw, b)
 
-    def weak_loss_volumes_from_features(self, f: torch.Tensor, hw, b: int) -> torch.Tensor:
+    def weak_loss_volumes_from_features(self, f: torch.Tensor, hw, b: int, return_delta: bool = False):
         """``weak_loss_volumes`` after the backbone: ``f`` = extract() of the
         2B images [source; target] (engine/trainer.py TrunkPrefetcher runs it
-        one step ahead on a side stream when the trunk is frozen)."""
+        one step ahead on a side stream when the trunk is frozen).  With
+        ``relocalization_k_size`` k > 1 the volumes are max-pooled k x k x k x k
+        before the NC stack; ``return_delta``: also the pool's offsets (``None``
+        without pooling)."""
         h, w = hw
+        if self.relocalization_k_size > 1:
+            amap, bmap = _pair_map_lists(b)
+            with segment("correlation"):
+                corr, delta = self._relocalized_volumes(f, hw, b, amap, bmap)
+            corr = self.process_correlation(corr)
+            return (corr, delta) if return_delta else corr
+        if return_delta:
+            return self.weak_loss_volumes_from_features(f, hw, b), None
         if isinstance(f, tuple):               # split operands (nc_precision / corr_dtype 'fp32')
             if _nc_ops.x3_dropped("corr"):     # precision ablation: bf16 correlation operands
                 f = (f[0], torch.zeros_like(f[1]))

@@ -8,7 +8,9 @@
   rolled negative pairs (train.py:137) without copying features.
 * ``correlation_pool2``: the InLoc relocalization path; GEMM with a fused
   2x2x2x2 max-pool epilogue (lib/model.py:177-191) -- only the pooled volume
-  and packed argmax offsets are written.
+  and packed argmax offsets are written.  It takes the same pair maps, and
+  bf16 features that require grad get the HIP backward ``corr_pool2_bwd``
+  (``CorrelationPool2Fn``; relocalized training with a trainable trunk).
 * IEEE-half inference (``corr_dtype='fp16'``, half_precision models as the
   reference's eval_inloc.py): ``l2norm_pack_f16`` operands on the f16 MFMA.
 * fp32-accurate inference ("bf16x3", ``corr_dtype='fp32'``): the L2-norm
@@ -237,18 +239,199 @@ def _block_order_index(h: int, w: int, k: int, device) -> torch.Tensor:
     return perm  # new row r takes old row perm[r]
 
 
+_BLOCK_ORDER_INV: dict = {}
+
+
+def block_order_inverse(h: int, w: int, k: int, device) -> torch.Tensor:
+    """Inverse of ``block_order_index``: natural row r sits at block-order row
+    ``inv[r]`` (cached like the permutation; read-only)."""
+    key = (h, w, k, str(device))
+    inv = _BLOCK_ORDER_INV.get(key)
+    if inv is None:
+        with torch.inference_mode(False):
+            inv = _BLOCK_ORDER_INV[key] = torch.argsort(_block_order_index(h, w, k, device))
+    return inv
+
+
+def _host_map(m, n: int):
+    """A pair map as a tuple of ints (``None``: identity over n images).  A GPU
+    tensor is read back (one host sync): callers on the training path pass
+    lists / CPU tensors."""
+    if m is None:
+        return tuple(range(n))
+    if torch.is_tensor(m):
+        return tuple(int(x) for x in m.reshape(-1).tolist())
+    return tuple(int(x) for x in m)
+
+
+_DEV_MAPS: dict = {}       # keyed by the map tuple: a trainer has one or two batch sizes, so a few entries
+
+
+def _device_map(m, device) -> torch.Tensor:
+    """int32 device tensor of a pair map given as a sequence or tensor (sequences cached)."""
+    if torch.is_tensor(m):
+        return m.to(device=device, dtype=torch.int32)
+    key = (tuple(m), str(device))
+    t = _DEV_MAPS.get(key)
+    if t is None:
+        with torch.inference_mode(False):
+            t = _DEV_MAPS[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
+    return t
+
+
+_BWD_TABLES: dict = {}     # likewise: one small table per distinct (maps, image counts, device)
+
+
+def pool2_bwd_table(amap, bmap, na: int, nb: int, device):
+    """Per-image volume lists of the pooled correlation's backward, built and
+    validated on the host: ``(aoff [na+1], avol [V], boff [nb+1], bvol [V],
+    amap [V], bmap [V])`` int32 on ``device``.  Image n of side A owns the
+    volumes ``avol[aoff[n]:aoff[n+1]]`` in ascending order (likewise B); every
+    map entry is in range and every volume appears exactly once per side.
+    Cached per (maps, na, nb, device)."""
+    am, bm = tuple(amap), tuple(bmap)
+    key = (am, bm, na, nb, str(device))
+    tab = _BWD_TABLES.get(key)
+    if tab is not None:
+        return tab
+    if len(am) != len(bm):
+        raise ValueError(f"amap has {len(am)} volumes, bmap {len(bm)}")
+    out = []
+    for name, mp, n in (("amap", am, na), ("bmap", bm, nb)):
+        bad = [x for x in mp if not 0 <= x < n]
+        if bad:
+            raise ValueError(f"{name} entries {bad} are outside [0, {n})")
+        lists = [[v for v, x in enumerate(mp) if x == img] for img in range(n)]
+        off = [0]
+        for ls in lists:
+            off.append(off[-1] + len(ls))
+        vol = [v for ls in lists for v in ls]
+        if sorted(vol) != list(range(len(mp))):
+            raise ValueError(f"{name}: every volume must appear exactly once in the image lists")
+        out += [off, vol]
+    with torch.inference_mode(False):
+        tab = tuple(torch.tensor(x, dtype=torch.int32, device=device) for x in (*out, am, bm))
+    _BWD_TABLES[key] = tab
+    return tab
+
+
+def _transposed_padded(x: torch.Tensor) -> torch.Tensor:
+    """[n, R, K] -> [n, K, ldr] with ldr = R rounded up to 32, zero past R (the
+    feature operand of corr_pool2_bwd: a lane's 8 reduced rows in 16 bytes)."""
+    n, r, k = x.shape
+    ldr = (r + 31) // 32 * 32
+    if ldr == r:
+        return x.transpose(1, 2).contiguous()
+    t = torch.zeros((n, k, ldr), dtype=x.dtype, device=x.device)
+    t[:, :, :r] = x.transpose(1, 2)
+    return t
+
+
+def corr_pool2_bwd(a: torch.Tensor, b: torch.Tensor, g: torch.Tensor, code: torch.Tensor, amap, bmap,
+                   hA: int, wA: int, hB: int, wB: int, need=(True, True)):
+    """Feature gradients of the fused pooled correlation on the HIP kernel
+    (csrc/corrpool_bwd.hip).  ``a`` [Na, hA*wA, K] / ``b`` [Nb, hB*wB, K] bf16
+    in 2x2-block row order, ``g`` fp32 and ``code`` uint8 [V, hA/2, wA/2, hB/2,
+    wB/2] (codes as ``corr_gemm_pool2`` writes them), ``amap`` / ``bmap`` host
+    sequences.  Returns (gA, gB) fp32 in block row order (``None`` where
+    ``need`` is false).  ``g`` enters the MFMA rounded to bf16 (round to nearest
+    even), as every gradient operand of the bf16 training path; products are
+    exact and accumulate in fp32 in a fixed order: two runs are bit-identical."""
+    if a.shape[2] % 16:
+        raise ValueError(f"corr_pool2_bwd needs a channel count that is a multiple of 16 (got {a.shape[2]})")
+    dev = a.device
+    aoff, avol, boff, bvol, am, bm = pool2_bwd_table(_host_map(amap, a.shape[0]), _host_map(bmap, b.shape[0]),
+                                                     a.shape[0], b.shape[0], dev)
+    V = am.numel()
+    g = g.reshape(V, hA // 2, wA // 2, hB // 2, wB // 2).float().contiguous()
+    code = code.reshape(g.shape).contiguous()
+    C = _ext.ext()
+    ga = gb = None
+    if need[0]:
+        ga = torch.empty(a.shape, dtype=torch.float32, device=dev)
+        C.corr_pool2_bwd(_transposed_padded(b), g, code, aoff, avol, bm, ga, 0, hA, wA, hB, wB)
+    if need[1]:
+        gb = torch.empty(b.shape, dtype=torch.float32, device=dev)
+        C.corr_pool2_bwd(_transposed_padded(a), g, code, boff, bvol, am, gb, 1, hA, wA, hB, wB)
+    _ext.count("corr_pool2_bwd")
+    return ga, gb
+
+
+class CorrelationPool2Fn(torch.autograd.Function):
+    """Fused correlation + 2x2x2x2 max-pool with a HIP backward into bf16
+    features (natural row order in and out; the block-order gather is inside)."""
+
+    @staticmethod
+    def forward(ctx, fa, fb, amap, bmap, dims, host_maps):
+        hA, wA, hB, wB = dims
+        pa = block_order_index(hA, wA, 2, fa.device)
+        pb = block_order_index(hB, wB, 2, fb.device)
+        a = fa.to(torch.bfloat16)[:, pa].contiguous()
+        b = fb.to(torch.bfloat16)[:, pb].contiguous()
+        shape = (amap.numel(), hA // 2, wA // 2, hB // 2, wB // 2)
+        val = torch.empty(shape, dtype=torch.float32, device=fa.device)
+        code = torch.empty(shape, dtype=torch.uint8, device=fa.device)
+        _ext.ext().corr_gemm_pool2(a, b, val, code, hA, wA, hB, wB, 1.0, amap, bmap)
+        ctx.save_for_backward(a, b, code)
+        ctx.dims, ctx.host_maps = dims, host_maps
+        ctx.dtypes = (fa.dtype, fb.dtype)
+        code = code.unsqueeze(1)
+        ctx.mark_non_differentiable(code)
+        return val.unsqueeze(1), code
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # the HIP result has no graph: a double backward raises
+    def backward(ctx, g, _gcode):
+        a, b, code = ctx.saved_tensors
+        hA, wA, hB, wB = ctx.dims
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        ga, gb = corr_pool2_bwd(a, b, g, code, *ctx.host_maps, hA, wA, hB, wB, need=need)
+        if ga is not None:
+            ga = ga[:, block_order_inverse(hA, wA, 2, ga.device)].to(ctx.dtypes[0])
+        if gb is not None:
+            gb = gb[:, block_order_inverse(hB, wB, 2, gb.device)].to(ctx.dtypes[1])
+        return ga, gb, None, None, None, None
+
+
 def correlation_pool2(fa: torch.Tensor, fb: torch.Tensor, hA: int, wA: int, hB: int, wB: int,
-                      packed: bool = False):
-    """Fused correlation + maxpool4d(k=2). fa [V, hA*wA, C], fb [V, hB*wB, C]
-    (natural row order).  Returns (pooled [V,1,hA/2,wA/2,hB/2,wB/2] fp32,
-    (di, dj, dk, dl) uint8 offsets of the same shape) -- or, ``packed``, the
-    single uint8 volume of 2-bit codes (``decode_offsets``)."""
-    V = fa.shape[0]
+                      packed: bool = False, amap=None, bmap=None):
+    """Fused correlation + maxpool4d(k=2). fa [Na, hA*wA, C], fb [Nb, hB*wB, C]
+    (natural row order); volume v is the pair (fa[amap[v]], fb[bmap[v]]), the
+    maps (int sequences or int tensors) defaulting to the identity.  Returns
+    (pooled [V,1,hA/2,wA/2,hB/2,wB/2] fp32, (di, dj, dk, dl) uint8 offsets of
+    the same shape) -- or, ``packed``, the single uint8 volume of 2-bit codes
+    (``decode_offsets``).
+
+    bf16 (or fp32, cast to bf16) features that require grad go through
+    ``CorrelationPool2Fn``: the backward is the HIP kernel of
+    csrc/corrpool_bwd.hip, whose MFMA operand holds the incoming gradient
+    rounded to bf16 (see ``corr_pool2_bwd``).  Pass the maps as sequences or CPU
+    tensors there: a GPU map tensor is read back once to build the per-image
+    volume lists.  fp8 / IEEE-half operands are inference-only."""
+    mapped = amap is not None or bmap is not None
     fp8 = fa.dtype == FP8
     scale = 1.0 / (FP8_FEAT_SCALE * FP8_FEAT_SCALE) if fp8 else 1.0
     if not _ext.use_hip(fa):
-        corr = torch.bmm(fa.float(), fb.float().transpose(1, 2)).view(V, 1, hA, wA, hB, wB) * scale
+        a, b = fa.float(), fb.float()
+        if mapped:
+            a = a[torch.as_tensor(_host_map(amap, fa.shape[0]), dtype=torch.long, device=fa.device)]
+            b = b[torch.as_tensor(_host_map(bmap, fb.shape[0]), dtype=torch.long, device=fb.device)]
+        corr = torch.bmm(a, b.transpose(1, 2)).view(a.shape[0], 1, hA, wA, hB, wB) * scale
         return ref.maxpool4d(corr, 2)
+    if torch.is_grad_enabled() and (fa.requires_grad or fb.requires_grad):
+        if fp8 or fa.dtype == torch.float16 or fb.dtype == torch.float16:
+            raise RuntimeError("correlation_pool2: fp8 / fp16 operands are inference-only (no backward); "
+                               "use bf16 features for training")
+        ha_map, hb_map = _host_map(amap, fa.shape[0]), _host_map(bmap, fb.shape[0])
+        val, code = CorrelationPool2Fn.apply(fa, fb, _device_map(amap if amap is not None else ha_map, fa.device),
+                                             _device_map(bmap if bmap is not None else hb_map, fa.device),
+                                             (hA, wA, hB, wB), (ha_map, hb_map))
+        return (val, code) if packed else (val, decode_offsets(code))
+    am = bm = None
+    if mapped:
+        am = _device_map(amap if amap is not None else range(fa.shape[0]), fa.device)
+        bm = _device_map(bmap if bmap is not None else range(fb.shape[0]), fa.device)
+    V = am.numel() if mapped else fa.shape[0]
     pa = block_order_index(hA, wA, 2, fa.device)
     pb = block_order_index(hB, wB, 2, fb.device)
     if fp8:
@@ -260,7 +443,10 @@ def correlation_pool2(fa: torch.Tensor, fb: torch.Tensor, hA: int, wA: int, hB: 
     shape = (V, hA // 2, wA // 2, hB // 2, wB // 2)
     val = torch.empty(shape, dtype=torch.float32, device=fa.device)
     code = torch.empty(shape, dtype=torch.uint8, device=fa.device)
-    _ext.ext().corr_gemm_pool2(a, b, val, code, hA, wA, hB, wB, scale)
+    if mapped:
+        _ext.ext().corr_gemm_pool2(a, b, val, code, hA, wA, hB, wB, scale, am, bm)
+    else:
+        _ext.ext().corr_gemm_pool2(a, b, val, code, hA, wA, hB, wB, scale)
     if packed:
         return val.unsqueeze(1), code.unsqueeze(1)
     return val.unsqueeze(1), decode_offsets(code.unsqueeze(1))

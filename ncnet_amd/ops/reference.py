@@ -101,6 +101,36 @@ def maxpool4d(corr4d: torch.Tensor, k_size: int):
     return vals, tuple(t.unsqueeze(1) for t in (d_i, d_j, d_k, d_l))
 
 
+def corr_pool2_bwd(fa: torch.Tensor, fb: torch.Tensor, g: torch.Tensor, offsets, amap, bmap, hA: int, wA: int,
+                   hB: int, wB: int, quantize_g: bool = False):
+    """Feature gradients of ``maxpool4d(bmm(fa[amap], fb[bmap]^T), 2)`` in scatter
+    form: ``g`` [V,(1,)hA/2,wA/2,hB/2,wB/2] goes to the full-resolution volume at
+    the argmax ``offsets`` (di, dj, dk, dl), then two ``bmm`` and ``index_add_``
+    over the maps.  fa [Na, hA*wA, C], fb [Nb, hB*wB, C] in natural row order;
+    works in their dtype and returns (gA, gB) of their shapes.  ``quantize_g``:
+    round ``g`` to bf16 first (what the HIP kernel's MFMA operand holds)."""
+    V = g.shape[0]
+    pa, pb, qa, qb = hA // 2, wA // 2, hB // 2, wB // 2
+    dev, dt = fa.device, fa.dtype
+    g = g.reshape(V, pa, pb, qa, qb)
+    if quantize_g:
+        g = g.to(torch.bfloat16)
+    g = g.to(dt)
+    di, dj, dk, dl = (torch.as_tensor(d, device=dev).reshape(V, pa, pb, qa, qb).long() for d in offsets)
+    ar = lambda n, pos: torch.arange(n, device=dev).view([n if a == pos else 1 for a in range(5)])   # noqa: E731
+    row_a = (2 * ar(pa, 1) + di) * wA + 2 * ar(pb, 2) + dj
+    row_b = (2 * ar(qa, 3) + dk) * wB + 2 * ar(qb, 4) + dl
+    M, N = hA * wA, hB * wB
+    full = torch.zeros(V, M * N, dtype=dt, device=dev)
+    full.scatter_(1, (row_a * N + row_b).reshape(V, -1), g.reshape(V, -1))
+    full = full.view(V, M, N)
+    am = torch.as_tensor(amap, device=dev).long()
+    bm = torch.as_tensor(bmap, device=dev).long()
+    ga = torch.zeros_like(fa).index_add_(0, am, torch.bmm(full, fb[bm]))
+    gb = torch.zeros_like(fb).index_add_(0, bm, torch.bmm(full.transpose(1, 2), fa[am]))
+    return ga, gb
+
+
 def conv4d_weight_to_std(weight_ref: torch.Tensor) -> torch.Tensor:
     """[k, out, in, k, k, k] (checkpoint layout) -> [out, in, k, k, k, k]."""
     return weight_ref.permute(1, 2, 0, 3, 4, 5)

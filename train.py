@@ -103,6 +103,9 @@ def build_parser():
     p.add_argument("--result-model-dir", type=str, default="trained_models", help="path to trained models folder")
     p.add_argument("--fe_finetune_params", type=int, default=0, help="number of layers to finetune")
     # extensions
+    p.add_argument("--relocalization_k_size", type=int, default=0, metavar="K",
+                   help="max-pool the correlation k x k x k x k before NeighConsensus; with --image_size 800 and K = 2 "
+                        "the NC stack runs at the 400 px shape")
     p.add_argument("--synthetic", type=int, default=0)
     p.add_argument("--num_workers", type=int, default=-1,
                    help="DataLoader decode workers per rank (-1: min(8, cpus per rank) on GPU, 0 on CPU)")
@@ -220,6 +223,16 @@ def main(argv=None):
         if getattr(args, flag) and ((args.synthetic and not warp) or args.cpu_resize):
             raise SystemExit(f"--{flag} works on the uint8 input path (decoded image files, resized on the device); "
                              f"--{'synthetic' if args.synthetic else 'cpu_resize'} batches carry float images")
+    k_reloc = args.relocalization_k_size
+    if k_reloc < 0:
+        raise SystemExit("--relocalization_k_size must be >= 0")
+    if k_reloc > 1:
+        if args.image_size % (16 * k_reloc):
+            raise SystemExit(f"--relocalization_k_size {k_reloc}: the feature grid (--image_size {args.image_size} / 16 "
+                             f"= {args.image_size / 16:g} cells) must be a multiple of K")
+        if args.fe_finetune_params > 0 and k_reloc != 2:
+            raise SystemExit("--fe_finetune_params > 0 trains through the pooled correlation, whose backward exists "
+                             "for --relocalization_k_size 2 (even feature grids) only")
     augment = None
     if args.augment or warp:                       # --loss warp: the ranges of the two views
         try:
@@ -239,7 +252,8 @@ def main(argv=None):
     # --resume rebuilds the NC architecture from the checkpoint's args, like --checkpoint
     model = ImMatchNet(use_cuda=ctx.device.type == "cuda", checkpoint=(args.resume or args.checkpoint) or None,
                        ncons_kernel_sizes=args.ncons_kernel_sizes, ncons_channels=args.ncons_channels,
-                       dtype=args.dtype, nc_precision=args.nc_precision).to(ctx.device)
+                       dtype=args.dtype, nc_precision=args.nc_precision,
+                       relocalization_k_size=args.relocalization_k_size).to(ctx.device)
     # the saved Namespace must describe the architecture actually built
     args.ncons_kernel_sizes = list(model.NeighConsensus.kernel_sizes)
     args.ncons_channels = list(model.NeighConsensus.channels)
