@@ -15,6 +15,16 @@ them), ``check()`` the oracle assertions on them.  ``fn`` calls the extension
 through ``ncnet_amd.ops._ext.ext()``; the test swaps a poisoning proxy in (see
 ``poisoned``).  Nothing here touches the GPU at import time.
 
+This module holds the harness, the table and the exemptions.  The recipes of
+the Conv4d, weight-gradient, padded-plane, fused NC, trunk-conv, correlation
+GEMM and MutualMatching kernels live in tests/kernel_cases.py, where the
+kernels' oracle tests call the same functions at their own shapes; the cases
+defined below take their inputs and oracle from a module their test shares
+(tests/volume_stats_ref.py, tests/strong_loss_cases.py, tests/pv_scene.py,
+tests/test_gpu_pnp.py).  A new kernel gets one recipe in tests/kernel_cases.py,
+one parametrized oracle test at the kernel's shapes, and one ``_add`` line here
+at the smallest shapes that still exercise the kernel.
+
 Before a kernel joins the table its source was read for integers that come out
 of LDS and become an index or an address: such a word must have been written
 earlier in the same launch, else a poisoned value would be a wild address.
@@ -29,8 +39,12 @@ import functools
 
 import torch
 
-DEV = "cuda"
-NAN = float("nan")
+from tests.kernel_cases import (DEV, _ext_mod, _finite, _m7, _nan, _ref, relerr,
+                                conv1x16, conv1x16_x3, conv2d_nhwc, conv2d_nhwc_x3, conv16_blk_fwd, conv16_fwd,
+                                conv16_fwd_group_planes, conv16_fwd_x3, conv16f8_fwd, corr_gemm, corr_gemm_pool2,
+                                cout1_taps_fwd, mm_apply, mm_bwd, nc_fused_k3, nc_fused_k3_f8, pad_planes_transposed,
+                                wgrad1x16, wgrad16, wgrad16p)
+
 # zeros; NaN as fp32, as a bf16 pair, as an fp16 pair and as fp64 (byte 0x7F: the
 # e4m3 NaN; a huge positive int32); fp32 -inf, the bf16 pair (-inf, 0) -- the
 # identity value of the statistics kernels
@@ -113,133 +127,12 @@ EXEMPT = {
 
 
 # ---------------------------------------------------------------------------
-# helpers
-# ---------------------------------------------------------------------------
-def _ext_mod():
-    from ncnet_amd.ops import _ext
-    return _ext.ext()
-
-
-def _ref():
-    from ncnet_amd.ops import reference
-    return reference
-
-
-def bf(x):
-    return x.to(torch.bfloat16).double()
-
-
-def relerr(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
-
-
-def rel_l2(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
-
-
-def _nan(shape, dtype=torch.float32):
-    return torch.full(tuple(shape), NAN, device=DEV).to(dtype)
-
-
-def _m7(shape, dtype=torch.int32):
-    return torch.full(tuple(shape), -7, dtype=dtype, device=DEV)
-
-
-def _finite(t):
-    assert torch.isfinite(t.float()).all(), "an output element is NaN / Inf (never written, or stale LDS reached it)"
-
-
-# ---------------------------------------------------------------------------
 # Conv4d forward kernels
 # ---------------------------------------------------------------------------
-def cout1_taps_fwd(shape, cin, relu):
-    """test_gpu_kernels.py::test_cout1_taps_fwd: fp64 Conv4d oracle, relerr < 1e-4."""
-    from ncnet_amd.ops.packing import cout1_taps_weights
-    ref = _ref()
-    torch.manual_seed(3)
-    ks = 5
-    V, I, J, K, L = shape
-    x = torch.rand(V, cin, I, J, K, L, device=DEV)
-    w = torch.randn(1, cin, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(1, device=DEV) * 0.1 - (0.3 if relu else 0.0)
-    xcl = torch.zeros(V, I, J, K, L, 16, device=DEV, dtype=torch.bfloat16)
-    xcl[..., :cin] = x.permute(0, 2, 3, 4, 5, 1).to(torch.bfloat16)
-    wt = cout1_taps_weights(w).to(torch.bfloat16)
-    y = _nan((V, I, J, K, L))
-    assert _ext_mod().cout1_taps_fwd(xcl, wt, b, y, ks, relu)
-
-    def check():
-        yr = ref.conv4d(bf(x), ref.conv4d_weight_from_std(bf(w)), b.double())[:, 0]
-        if relu:
-            yr = torch.relu(yr)
-        _finite(y)
-        assert relerr(y, yr) < 1e-4, relerr(y, yr)
-    return {"y": y}, check
-
-
 for _shape, _cin in (((1, 1, 1, 25, 25), 16), ((1, 2, 4, 25, 25), 16), ((2, 4, 3, 25, 25), 10)):
     for _relu in (0, 1):
         _add(f"cout1_taps_fwd-{'x'.join(map(str, _shape))}-relu{_relu}", ["cout1_taps_fwd"], cout1_taps_fwd, _shape, _cin,
              _relu)
-
-
-def conv16_fwd(ks, epi, shape):
-    """test_gpu_kernels.py::test_conv16v4_matches_v3_bitwise / test_conv16v4_other_planes: fp64 oracle on
-    the same bf16 operands, relerr < 4e-3 (the final bf16 rounding)."""
-    from ncnet_amd.ops.packing import pack_w16
-    ref = _ref()
-    torch.manual_seed(1)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    w_std = torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(16, device=DEV) * 0.1
-    y = _nan(x.shape, torch.bfloat16)
-    _ext_mod().conv16_fwd(x, pack_w16(w_std), b if epi == 1 else None, m if epi == 2 else None, y, ks, epi)
-
-    def check():
-        z = ref.conv4d(x.double().permute(0, 5, 1, 2, 3, 4), ref.conv4d_weight_from_std(bf(w_std)), None)
-        want = torch.relu(z + b.double().view(1, 16, 1, 1, 1, 1)) if epi == 1 else \
-            z * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-        _finite(y)
-        e = relerr(y.permute(0, 5, 1, 2, 3, 4), want)
-        assert e < 4e-3, e
-    return {"y": y}, check
-
-
-def conv16_fwd_group_planes(ks, epi, shape, grp=2):
-    """conv16v2 in group-plane mode.  test_gpu_kernels.py::test_conv16_fwd_v2_epilogues: the sum over the
-    groups of fp64 plane convs of the same bf16 operands, relerr < 1e-2 (bf16 output), < 1e-4 (planar fp32)."""
-    from ncnet_amd.ops.packing import pack_w16_planes
-    torch.manual_seed(4)
-    V, I, J, K, L = shape
-    x = torch.rand(grp, V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    w = (torch.randn(grp, 16, 16, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-    b = torch.randn(16, device=DEV) * 0.1
-    m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    wp = pack_w16_planes(w).to(torch.bfloat16)
-    if epi == 4:
-        y = _nan((16, V, I, J, K, L))
-    else:
-        y = _nan((V, I, J, K, L, 16), torch.bfloat16)
-    _ext_mod().conv16_fwd(x, wp, b if epi == 1 else None, m if epi == 2 else None, y, ks, epi)
-
-    def check():
-        xx = x.double().permute(0, 1, 2, 3, 6, 4, 5).reshape(grp, V * I * J, 16, K, L)
-        yr = sum(torch.nn.functional.conv2d(xx[g], w[g].double(), padding=ks // 2) for g in range(grp))
-        yr = yr.reshape(V, I, J, 16, K, L).permute(0, 3, 1, 2, 4, 5)          # [V, 16, I, J, K, L]
-        _finite(y)
-        if epi == 4:
-            assert relerr(y.permute(1, 0, 2, 3, 4, 5), yr) < 1e-4
-            return
-        if epi == 1:
-            yr = torch.relu(yr + b.double().view(1, 16, 1, 1, 1, 1))
-        else:
-            yr = yr * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-        assert relerr(y.permute(0, 5, 1, 2, 3, 4), yr) < 1e-2
-    return {"y": y}, check
 
 
 for _ks in (5, 3):
@@ -256,111 +149,13 @@ for _ks in (5, 3):
 _add("conv16_fwd-v2-groups-k5-epi4-1x3x2x11x13", ["conv16_fwd"], conv16_fwd_group_planes, 5, 4, (1, 3, 2, 11, 13))
 
 
-def conv16_blk_fwd(ks, shape, cin, relu):
-    """test_gpu_kernels.py::test_conv16_blk_fwd: fp64 Conv4d oracle, relerr < 1e-4."""
-    from ncnet_amd.ops.packing import blk_out_weights, pack_w16_planes
-    ref = _ref()
-    torch.manual_seed(1)
-    V, I, J, K, L = shape
-    x = torch.rand(V, cin, I, J, K, L, device=DEV)
-    w = torch.randn(1, cin, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(1, device=DEV) * 0.1 - (0.3 if relu else 0.0)
-    xcl = torch.zeros(V, I, J, K, L, 16, device=DEV, dtype=torch.bfloat16)
-    xcl[..., :cin] = x.permute(0, 2, 3, 4, 5, 1).to(torch.bfloat16)
-    y = _nan((V, I, J, K, L))
-    _ext_mod().conv16_blk_fwd(xcl, pack_w16_planes(blk_out_weights(w)), b, y, ks, relu)
-
-    def check():
-        yr = ref.conv4d(bf(x), ref.conv4d_weight_from_std(bf(w)), b.double())[:, 0]
-        if relu:
-            yr = torch.relu(yr)
-        _finite(y)
-        assert relerr(y, yr) < 1e-4
-    return {"y": y}, check
-
-
 _add("conv16_blk_fwd-k5-1x5x6x9x7-relu1", ["conv16_blk_fwd"], conv16_blk_fwd, 5, (1, 5, 6, 9, 7), 16, 1)
 _add("conv16_blk_fwd-k3-1x5x6x9x7-relu0", ["conv16_blk_fwd"], conv16_blk_fwd, 3, (1, 5, 6, 9, 7), 10, 0)
-
-
-def conv16f8_fwd(ks, shape, grp):
-    """test_gpu_kernels.py::test_conv16_fp8_kernel: fp64 math on the same e4m3 values; the fp8 output
-    within rel. L2 0.04 (e4m3 rounding), the planar fp32 output of group-plane mode relerr < 1e-4."""
-    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
-    ref = _ref()
-    F8 = torch.float8_e4m3fn
-    torch.manual_seed(21)
-    V, I, J, K, L = shape
-    wsc = 64.0
-    if not grp:
-        x = (torch.rand(V, I, J, K, L, 16, device=DEV) * 2).to(F8)
-        w = (torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-        wq = (pack_w16(w).float() * wsc).to(F8)
-        b = torch.randn(16, device=DEV) * 0.1
-        y = _nan((V, I, J, K, L, 16), F8)
-        _ext_mod().conv16f8_fwd(x, wq, b, y, ks, 1, 1.0 / wsc)
-
-        def check():
-            wr = (w * wsc).to(F8).double() / wsc
-            yr = ref.conv4d(x.double().permute(0, 5, 1, 2, 3, 4), ref.conv4d_weight_from_std(wr), b.double())
-            _finite(y)
-            assert rel_l2(y.float(), torch.relu(yr).permute(0, 2, 3, 4, 5, 1)) < 0.04
-        return {"y": y.view(torch.uint8)}, check
-    wp = (torch.randn(grp, 16, 16, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-    wpq = (pack_w16_planes(wp).float() * wsc).to(F8)
-    x2 = (torch.rand(grp, V, I, J, K, L, 16, device=DEV) * 2).to(F8)
-    z = _nan((16, V, I, J, K, L))
-    _ext_mod().conv16f8_fwd(x2, wpq, None, z, ks, 4, 1.0 / wsc)
-
-    def check():
-        wpr = (wp * wsc).to(F8).double() / wsc
-        xx = x2.double().permute(0, 1, 2, 3, 6, 4, 5).reshape(grp, V * I * J, 16, K, L)
-        zr = sum(torch.nn.functional.conv2d(xx[g], wpr[g], padding=ks // 2) for g in range(grp))
-        zr = zr.reshape(V, I, J, 16, K, L).permute(3, 0, 1, 2, 4, 5)
-        _finite(z)
-        assert relerr(z, zr) < 1e-4
-    return {"z": z}, check
 
 
 for _ks in (5, 3):
     _add(f"conv16f8_fwd-k{_ks}-1x3x2x11x13-epi1", ["conv16f8_fwd"], conv16f8_fwd, _ks, (1, 3, 2, 11, 13), 0)
     _add(f"conv16f8_fwd-k{_ks}-1x3x2x11x13-groups-epi4", ["conv16f8_fwd"], conv16f8_fwd, _ks, (1, 3, 2, 11, 13), 2)
-
-
-def _split(t):
-    hi = t.to(torch.bfloat16)
-    return hi, (t - hi.float()).to(torch.bfloat16)
-
-
-def conv16_fwd_x3(grp, plane, epi, ks, vij):
-    """test_gpu_x3.py::_conv16_x3_vs_emulator: hi + lo against the fp64 emulator, rel. L2 < 2e-5."""
-    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
-    torch.manual_seed(3)
-    V, I, J = vij
-    shp = (V, I, J, plane, plane)
-    x = torch.randn(((grp,) if grp else ()) + shp + (16,), device=DEV)
-    xh, xl = _split(x)
-    if grp:
-        w, pack = torch.randn(grp, 16, 16, ks, ks, device=DEV) * 0.05, pack_w16_planes
-    else:
-        w, pack = torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05, pack_w16
-    whi = w.to(torch.bfloat16).float()
-    wp2 = torch.stack((pack(whi), pack(w - whi))).contiguous()
-    bias = torch.rand(16, device=DEV) * 0.1 if epi == 1 else None
-    m = torch.randn(shp + (16,), device=DEV).to(torch.bfloat16) if epi == 2 else None
-    yh, yl = _nan(shp + (16,), torch.bfloat16), _nan(shp + (16,), torch.bfloat16)
-    _ext_mod().conv16_fwd_x3(xh, xl, wp2, bias, m, yh, yl, ks, epi)
-
-    def check():
-        from tests import emu_ext
-        eh = torch.empty(shp + (16,), dtype=torch.float64)
-        el = torch.empty_like(eh)
-        emu_ext.conv16_fwd_x3(xh.cpu(), xl.cpu(), wp2.cpu(), None if bias is None else bias.cpu(),
-                              None if m is None else m.cpu(), eh, el, ks, epi)
-        _finite(yh), _finite(yl)
-        err = rel_l2(yh.double().cpu() + yl.double().cpu(), eh + el)
-        assert err < 2e-5, err
-    return {"yh": yh, "yl": yl}, check
 
 
 _add("conv16_fwd_x3-v4-k5-25-epi1", ["conv16_fwd"], conv16_fwd_x3, 0, 25, 1, 5, (1, 2, 6))
@@ -371,35 +166,6 @@ _add("conv16_fwd_x3-v2-groups-k5-9-epi1", ["conv16_fwd"], conv16_fwd_x3, 2, 9, 1
 # ---------------------------------------------------------------------------
 # weight gradients of the 16 -> 16 layer
 # ---------------------------------------------------------------------------
-def wgrad16(variant, ks, shape):
-    """test_gpu_kernels.py::test_wgrad16_kernel: autograd of the fp64 oracle, relerr < 1e-3."""
-    import importlib
-    nc = importlib.import_module("ncnet_amd.ops.nc.layers")
-    ref = _ref()
-    torch.manual_seed(11)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    g = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    if variant == 3:
-        assert nc.wgrad_v3_ok(shape, ks)
-        ng = nc.wgrad_v3_groups(shape, ks)
-    else:
-        ng = nc.wgrad_groups(ks, nc._nitems(shape))
-    part = _nan((2 * ng, ks * ks, ks * ks, 16, 16))
-    partb = _nan((2 * ng, 16))
-    _ext_mod().wgrad16(x, g, part, partb, ks, 0, variant)
-
-    def check():
-        wr = torch.zeros(ks, 16, 16, ks, ks, ks, device=DEV, dtype=torch.float64, requires_grad=True)
-        yr = ref.conv4d(x.double().permute(0, 5, 1, 2, 3, 4), wr, None)
-        (yr * g.double().permute(0, 5, 1, 2, 3, 4)).sum().backward()
-        dstd = ref.conv4d_weight_to_std(wr.grad)
-        _finite(part), _finite(partb)
-        assert relerr(nc._reduce_wgrad16(part.sum(0), ks, 16, 16), dstd) < 1e-3
-        assert relerr(partb.sum(0), g.double().sum(dim=(0, 1, 2, 3, 4))) < 1e-3
-    return {"part": part, "partb": partb}, check
-
-
 for _shape in ((1, 3, 4, 25, 25), (1, 5, 7, 7, 9)):
     _s = "x".join(map(str, _shape))
     for _ks in (5, 3):
@@ -410,33 +176,6 @@ _add("wgrad16-v4-k5-1x3x4x25x25", ["wgrad16v3"], wgrad16, 3, 5, (1, 3, 4, 25, 25
 _add("wgrad16-v4-k3-1x3x4x25x25", ["wgrad16v3"], wgrad16, 3, 3, (1, 3, 4, 25, 25), tuning=(("wgrad_v3", 0),))
 
 
-def wgrad16p(ks, shape, nx, ng):
-    """test_gpu_kernels.py::test_wgrad16p: the fp64 plane-conv definition, relerr < 1e-4."""
-    import torch.nn.functional as F
-    torch.manual_seed(2)
-    V, I, J, K, L = shape
-    x = (torch.rand((nx,) + shape + (16,), device=DEV) - 0.3).to(torch.bfloat16)
-    g = torch.randn((ng,) + shape + (16,), device=DEV).to(torch.bfloat16)
-    part = _nan((64, nx * ng, ks * ks, 16, 16))
-    partb = _nan((64, nx * ng, 16))
-    _ext_mod().wgrad16p(x, g, part, partb, ks)
-
-    def check():
-        _finite(part), _finite(partb)
-        s, sb = part.sum(0), partb.sum(0)
-        P = ks // 2
-        for a in range(nx):
-            for n in range(ng):
-                xx = x[a].double().reshape(V * I * J, K, L, 16).permute(0, 3, 1, 2)
-                gg = g[n].double().reshape(V * I * J, K, L, 16).permute(0, 3, 1, 2)
-                xp = F.pad(xx, (P, P, P, P))
-                want = torch.stack([torch.einsum("nckl,nokl->co", xp[:, :, dk:dk + K, dl:dl + L], gg)
-                                    for dk in range(ks) for dl in range(ks)])
-                assert relerr(s[a * ng + n], want) < 1e-4
-                assert relerr(sb[a * ng + n], gg.sum(dim=(0, 2, 3))) < 1e-4
-    return {"part": part, "partb": partb}, check
-
-
 _add("wgrad16p-k5-1x3x4x25x25-ngg2", ["wgrad16p"], wgrad16p, 5, (1, 3, 4, 25, 25), 1, 2)
 _add("wgrad16p-k5-1x3x4x25x25-nsets2", ["wgrad16p"], wgrad16p, 5, (1, 3, 4, 25, 25), 2, 1)
 _add("wgrad16p-k3-1x5x7x7x9-ngg2", ["wgrad16p"], wgrad16p, 3, (1, 5, 7, 7, 9), 1, 2)
@@ -445,97 +184,6 @@ _add("wgrad16p-k3-1x5x7x7x9-ngg2", ["wgrad16p"], wgrad16p, 3, (1, 5, 7, 7, 9), 1
 # ---------------------------------------------------------------------------
 # the 1-channel layers on padded planes
 # ---------------------------------------------------------------------------
-def _pad_1ch(x3, K, L, ks, trans=0, I=None, J=None):
-    """x3 [V, R, C] -> padded bf16 planes [V * R, PPL] (trans: [V * C, PPL] of the A <-> B swap)."""
-    C = _ext_mod()
-    V, R, Cc = x3.shape
-    kk, ll = (I, J) if trans else (K, L)
-    _, ppl = C.pad_geom(kk, ll, ks)
-    y = torch.zeros((V * (Cc if trans else R), ppl), dtype=torch.bfloat16, device=DEV)
-    C.pad_planes(x3.contiguous(), y, kk, ll, ks, trans)
-    return y
-
-
-def conv1x16(ks, shape, epi):
-    """test_gpu_kernels.py::_conv1x16_vs_oracle: fp64 oracle, relerr < 1e-2."""
-    from ncnet_amd.ops.packing import pack_w1x
-    ref = _ref()
-    torch.manual_seed(3)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    w = torch.randn(16, 1, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(16, device=DEV) * 0.1
-    m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    xp = _pad_1ch(x.reshape(V, I * J, K * L), K, L, ks)
-    y = _nan((V, I, J, K, L, 16), torch.bfloat16)
-    assert _ext_mod().conv1x16(xp, pack_w1x(w), b if epi == 1 else None, m if epi == 2 else None, y, ks, epi)
-
-    def check():
-        z = ref.conv4d(x.double().unsqueeze(1), ref.conv4d_weight_from_std(bf(w)), None)
-        want = torch.relu(z + b.double().view(1, 16, 1, 1, 1, 1)) if epi == 1 else \
-            z * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-        _finite(y)
-        assert relerr(y.permute(0, 5, 1, 2, 3, 4), want) < 1e-2
-    return {"y": y}, check
-
-
-def conv1x16_x3(ks, shape):
-    """conv1x16's bf16x3 mode (epi 1 | 4) as ops/nc/x3.py launches it: hi + lo against the fp64 Conv4d of
-    the unsplit fp32 operands.  Bound: rel. L2 < 2e-4, what test_gpu_x3.py::test_x3_fused_matches_fp64
-    holds the stack built on this launch to."""
-    from ncnet_amd.ops.packing import pack_w1x
-    ref = _ref()
-    torch.manual_seed(7)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I * J, K * L, device=DEV)
-    w = torch.randn(16, 1, ks, ks, ks, ks, device=DEV) * (0.5 / ks ** 2)
-    b = torch.rand(16, device=DEV) * 0.1
-    xh, xl = _split(x)
-    xs = torch.stack((_pad_1ch(xh, K, L, ks), _pad_1ch(xl, K, L, ks))).contiguous()
-    whi = w.to(torch.bfloat16).float()
-    wa = torch.stack((pack_w1x(whi), pack_w1x(w - whi))).to(torch.bfloat16).contiguous()
-    a = _nan((2, V, I, J, K, L, 16), torch.bfloat16)
-    assert _ext_mod().conv1x16(xs, wa, b, None, a, ks, 1 | 4)
-
-    def check():
-        xq = (xh.double() + xl.double()).reshape(V, 1, I, J, K, L)
-        wq = whi.double() + (w - whi).to(torch.bfloat16).double()
-        want = torch.relu(ref.conv4d(xq, ref.conv4d_weight_from_std(wq), b.double()))
-        _finite(a)
-        err = rel_l2((a[0].double() + a[1].double()).permute(0, 5, 1, 2, 3, 4), want)
-        assert err < 2e-4, err
-    return {"a": a}, check
-
-
-def wgrad1x16(ks, shape, G, bias):
-    """test_gpu_kernels.py::test_wgrad1x16_vs_oracle: autograd of the fp64 oracle, relerr < 1e-4."""
-    ref = _ref()
-    torch.manual_seed(21)
-    V, I, J, K, L = shape
-    x1 = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    d = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    nt = ks * ks
-    part = _nan((G, nt, 32, 16))
-    partb = _nan((G, 16)) if bias else None
-    assert _ext_mod().wgrad1x16(d, _pad_1ch(x1.reshape(V, I * J, K * L), K, L, ks), part, partb, ks)
-
-    def check():
-        _finite(part)
-        R = part.sum(0)[:, :nt, :]
-        wr = torch.zeros(ks, 16, 1, ks, ks, ks, device=DEV, dtype=torch.float64, requires_grad=True)
-        yr = ref.conv4d(x1.double().unsqueeze(1), wr, None)
-        (yr * d.double().permute(0, 5, 1, 2, 3, 4)).sum().backward()
-        want = ref.conv4d_weight_to_std(wr.grad)[:, 0].reshape(16, nt, nt)
-        assert relerr(R.permute(2, 1, 0), want) < 1e-4
-        if bias:
-            _finite(partb)
-            assert relerr(partb.sum(0), d.double().sum(dim=(0, 1, 2, 3, 4))) < 1e-4
-    outs = {"part": part}
-    if bias:
-        outs["partb"] = partb
-    return outs, check
-
-
 for _ks, _shape in ((5, (1, 2, 6, 25, 25)), (5, (1, 3, 4, 20, 20)), (3, (1, 4, 5, 25, 25))):
     _s = "x".join(map(str, _shape))
     for _epi in (1, 2):
@@ -546,85 +194,12 @@ for _ks, _shape in ((5, (1, 2, 6, 25, 25)), (5, (1, 3, 4, 20, 20)), (3, (1, 4, 5
 _add("conv1x16_x3-k5-1x2x6x25x25", ["conv1x16", "pad_planes"], conv1x16_x3, 5, (1, 2, 6, 25, 25))
 
 
-def pad_planes_transposed():
-    """test_gpu_kernels.py::test_pad_planes_transposed (the trans = 1 kernel stages a tile in LDS): equal to
-    the plain padding of the swapped volume."""
-    torch.manual_seed(4)
-    V, I, J, K, L = 2, 9, 11, 9, 11
-    x = torch.randn(V, I, J, K, L, device=DEV)
-    a = _pad_1ch(x.reshape(V, I * J, K * L), K, L, 5, 1, I, J)
-
-    def check():
-        b = _pad_1ch(x.permute(0, 3, 4, 1, 2).contiguous().reshape(V, K * L, I * J), I, J, 5)
-        assert torch.equal(a, b)
-    return {"planes": a}, check
-
-
 _add("pad_planes-transposed", ["pad_planes"], pad_planes_transposed)
 
 
 # ---------------------------------------------------------------------------
 # fused InLoc NC stack
 # ---------------------------------------------------------------------------
-def nc_fused_k3(shape, cfg, seed):
-    """test_gpu_kernels.py::test_nc_fused_k3_vs_quantized_oracle / ..._one_wide_workgroup: the quantized
-    fp64 oracle, relerr < 2e-3."""
-    import importlib
-    from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
-    ref = _ref()
-    torch.manual_seed(seed)
-    V, I, J, K, L = shape
-    w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
-    w2 = torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.1
-    b1, b2 = torch.rand(16, device=DEV) * 0.1 - 0.03, torch.rand(1, device=DEV) * 0.1
-    ws = [ref.conv4d_weight_from_std(w1), ref.conv4d_weight_from_std(w2)]
-    x0 = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    wts = nc._fused_weights(ws, [b1, b2])
-    y = _nan((V, I, J, K, L))
-    tk, tl, R, IR = nc.fused_tiles(V, I, J, K, L) if cfg is None else (cfg[2], cfg[3], cfg[0], cfg[1])
-    _ext_mod().nc_fused_k3(x0, *wts, y, R, IR, tk, tl)
-
-    def check():
-        yr = qo.nc_stack(x0.double().unsqueeze(1), [w1.double(), w2.double()], [b1.double(), b2.double()])
-        _finite(y)
-        assert relerr(y, yr.squeeze(1)) < 2e-3
-    return {"y": y}, check
-
-
-def _f8q(t, s):
-    return (t.double() * s).float().clamp(-448, 448).to(torch.float8_e4m3fn).double() / s
-
-
-def nc_fused_k3_f8(shape, cfg):
-    """test_gpu_kernels.py::test_nc_fused_k3_f8_vs_quantized_oracle: fp64 math with the same e4m3
-    roundings, relerr < 2e-2 and rel. L2 < 2e-3."""
-    import importlib
-    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
-    ref = _ref()
-    torch.manual_seed(41)
-    V, I, J, K, L = shape
-    w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
-    w2 = torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.1
-    b1, b2 = torch.rand(16, device=DEV) * 0.1 - 0.03, torch.rand(1, device=DEV) * 0.1
-    ws = [ref.conv4d_weight_from_std(w1), ref.conv4d_weight_from_std(w2)]
-    x0 = (torch.rand(V, I, J, K, L, device=DEV) ** 3).to(torch.bfloat16)
-    tens, (sx, inv1, sh, inv2) = nc._fused_weights_f8_build(ws, [b1, b2])
-    y = _nan((V, I, J, K, L))
-    tk, tl, R, IR = nc.fused_tiles(V, I, J, K, L) if cfg is None else (cfg[2], cfg[3], cfg[0], cfg[1])
-    _ext_mod().nc_fused_k3_f8(x0, *tens, y, R, IR, tk, tl, sx, inv1, sh, inv2)
-
-    def check():
-        sw1, sw2 = 1.0 / (inv1 * sx), 1.0 / (inv2 * sh)
-        xq = _f8q(x0, sx).unsqueeze(1)
-        h = torch.relu(ref.conv4d(xq, ref.conv4d_weight_from_std(_f8q(w1, sw1))) + b1.double().view(1, -1, 1, 1, 1, 1))
-        h = _f8q(h, sh)
-        yr = torch.relu(ref.conv4d(h, ref.conv4d_weight_from_std(_f8q(w2, sw2))) + b2.double().view(1, -1, 1, 1, 1, 1))
-        _finite(y)
-        assert relerr(y, yr.squeeze(1)) < 2e-2 and rel_l2(y, yr.squeeze(1)) < 2e-3
-    return {"y": y}, check
-
-
 for _cfg in (None, (3, 4, 6, 7), (5, 2, 9, 11)):
     _c = "auto" if _cfg is None else "x".join(map(str, _cfg))
     _add(f"nc_fused_k3-2x9x13x11x14-{_c}", ["nc_fused_k3"], nc_fused_k3, (2, 9, 13, 11, 14), _cfg, 21)
@@ -636,62 +211,6 @@ _add("nc_fused_k3-one-wide-workgroup", ["nc_fused_k3"], nc_fused_k3, (1, 6, 26, 
 # ---------------------------------------------------------------------------
 # correlation GEMMs
 # ---------------------------------------------------------------------------
-def corr_gemm(kind, M, N, K, out16):
-    """fp64 GEMM of the same operand values.  fp32 C: rel. L2 < 1e-5 (test_gpu_f16.py::test_corr_gemm_f16;
-    exact products, fp32 sums), fp8 operands relerr < 1e-4 (test_gpu_kernels.py::
-    test_fp8_l2norm_and_correlation); 16-bit C: 1e-3 (f16) / 4e-3 (bf16), test_gpu_f16.py::
-    test_corr_gemm_16bit_out.  fp8 operands need K % 16 == 0."""
-    torch.manual_seed(1)
-    dt = {"f16": torch.float16, "bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}[kind]
-    a = (torch.randn(2, M, K, device=DEV) * 0.25).to(dt)
-    b = (torch.randn(2, N, K, device=DEV) * 0.25).to(dt)
-    scale = 0.5 if kind == "fp8" else 1.0
-    amap = torch.tensor([1, 0], device=DEV, dtype=torch.int32)
-    bmap = torch.tensor([0, 0], device=DEV, dtype=torch.int32)
-    cdt = torch.float32 if not out16 else torch.float16 if kind == "f16" else torch.bfloat16
-    c = _nan((2, M, N), cdt)
-    _ext_mod().corr_gemm(a, b, c, amap, bmap, scale)
-
-    def check():
-        want = scale * torch.bmm(a.float().double()[amap.long()], b.float().double()[bmap.long()].transpose(1, 2))
-        _finite(c)
-        if out16:
-            assert rel_l2(c, want) < (1e-3 if kind == "f16" else 4e-3)
-        elif kind == "fp8":
-            assert relerr(c, want) < 1e-4
-        else:
-            assert rel_l2(c, want) < 1e-5
-    return {"c": c}, check
-
-
-def corr_gemm_pool2(kind, K):
-    """test_gpu_f16.py::test_corr_pool2_f16_matches_unfused (rel. L2 < 1e-5 against pooling the full fp32
-    volume) for f16 / bf16; fp8: test_gpu_kernels.py::test_fp8_l2norm_and_correlation, relerr < 1e-4."""
-    from ncnet_amd.ops.correlation import FP8, FP8_FEAT_SCALE, correlation_pool2
-    ref = _ref()
-    torch.manual_seed(2)
-    hA, wA, hB, wB = 12, 16, 10, 14
-    fa = torch.nn.functional.normalize(torch.randn(1, hA * wA, K, device=DEV), dim=2)
-    fb = torch.nn.functional.normalize(torch.randn(1, hB * wB, K, device=DEV), dim=2)
-    if kind == "fp8":
-        fa, fb = (fa * FP8_FEAT_SCALE).to(FP8), (fb * FP8_FEAT_SCALE).to(FP8)
-    else:
-        dt = torch.float16 if kind == "f16" else torch.bfloat16
-        fa, fb = fa.to(dt), fb.to(dt)
-    val, code = correlation_pool2(fa, fb, hA, wA, hB, wB, packed=True)
-
-    def check():
-        s = 1.0 / FP8_FEAT_SCALE ** 2 if kind == "fp8" else 1.0
-        full = (torch.bmm(fa.double(), fb.double().transpose(1, 2)) * s).float().view(1, 1, hA, wA, hB, wB)
-        want, _ = ref.maxpool4d(full, 2)
-        _finite(val)
-        if kind == "fp8":
-            assert relerr(val, want) < 1e-4
-        else:
-            assert rel_l2(val, want) < 1e-5
-    return {"val": val, "code": code}, check
-
-
 for _v2 in (0, 1):
     _t = (("corr_v2", _v2),)
     for _kind in ("bf16", "f16", "fp8"):
@@ -711,68 +230,6 @@ for _v2 in (0, 1):
 # ---------------------------------------------------------------------------
 # feature-trunk convolutions
 # ---------------------------------------------------------------------------
-def conv2d_nhwc(cin, cout, k, stride, pad, res, relu, shape, dt, seed):
-    """test_gpu_kernels.py::_conv2d_nhwc_vs_fp64 / test_conv2d_nhwc_v3: F.conv2d in fp64 on the 16-bit
-    inputs, relerr < 1e-2."""
-    torch.manual_seed(seed)
-    cl = torch.channels_last
-    x = torch.randn(shape[0], cin, shape[1], shape[2], device=DEV).to(dt).contiguous(memory_format=cl)
-    w = (torch.randn(cout, cin, k, k, device=DEV) * 0.05).to(dt).contiguous(memory_format=cl)
-    b = torch.randn(cout, device=DEV)
-    ho, wo = (shape[1] + 2 * pad - k) // stride + 1, (shape[2] + 2 * pad - k) // stride + 1
-    r = torch.randn((shape[0], cout, ho, wo), device=DEV).to(dt).contiguous(memory_format=cl) if res else None
-    y = torch.full((shape[0], cout, ho, wo), NAN, dtype=dt, device=DEV).contiguous(memory_format=cl)
-    _ext_mod().conv2d_nhwc(x, w, b, r, y, stride, pad, 1 if relu else 0)
-
-    def check():
-        yr = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), stride, pad)
-        if res:
-            yr = yr + r.double()
-        if relu:
-            yr = torch.relu(yr)
-        _finite(y)
-        assert relerr(y, yr) < 1e-2, relerr(y, yr)
-    return {"y": y}, check
-
-
-def conv2d_nhwc_x3(cin, cout, k, stride, pad, res, relu, shape):
-    """test_gpu_x3.py::test_conv2d_x3_vs_fp64: the fp64 conv of the [hi | lo] pairs, rel. L2 < 3e-5."""
-    torch.manual_seed(5)
-    n, h, w = shape
-
-    def pairs(t):
-        hi = t.to(torch.bfloat16)
-        return torch.cat((hi, (t - hi.float()).to(torch.bfloat16)), -1).contiguous()
-
-    def unpair(p):
-        c = p.shape[-1] // 2
-        return p[..., :c].double() + p[..., c:].double()
-
-    x = torch.randn(n, h, w, cin, device=DEV)
-    wt = torch.randn(cout, cin, k, k, device=DEV) * (1.0 / (cin * k * k) ** 0.5)
-    b = torch.randn(cout, device=DEV) * 0.1
-    wcl = wt.permute(0, 2, 3, 1)
-    whi = wcl.to(torch.bfloat16)
-    w3 = torch.cat((whi, whi, (wcl - whi.float()).to(torch.bfloat16)), -1).contiguous()
-    xp = pairs(x)
-    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-    r = pairs(torch.randn((n, ho, wo, cout), device=DEV)) if res else None
-    y = _nan((n, ho, wo, 2 * cout), torch.bfloat16)
-    _ext_mod().conv2d_nhwc_x3(xp, w3, b, r, y, stride, pad, 1 if relu else 0)
-
-    def check():
-        want = torch.nn.functional.conv2d(unpair(xp).permute(0, 3, 1, 2), wt.double(), b.double(), stride, pad)
-        want = want.permute(0, 2, 3, 1)
-        if res:
-            want = want + unpair(r)
-        if relu:
-            want = torch.relu(want)
-        _finite(y)
-        err = rel_l2(unpair(y), want)
-        assert err < 3e-5, err
-    return {"y": y}, check
-
-
 _BF, _HF = torch.bfloat16, torch.float16
 _add("conv2d_nhwc-v1-64x64-3x3", ["conv2d_nhwc"], conv2d_nhwc, 64, 64, 3, 1, 1, False, True, (2, 19, 23), _BF, 17)
 _add("conv2d_nhwc-v1-128x256-1x1-residual", ["conv2d_nhwc"], conv2d_nhwc, 128, 256, 1, 1, 0, True, True, (2, 19, 23), _BF,
@@ -872,70 +329,6 @@ for _rt in (1, 2, 4):
              tuning=(("s2d_rt", _rt),))
 # chunked stats_cols (few wide columns: partials + merge)
 _add("stats_cols-1x70x7500-chunked", ["stats_cols"], stats_cols, "peaky", (1, 70, 7500), 1)
-
-
-def _mm_inputs(shape6, seed):
-    from tests import volume_stats_ref as VR
-    c = VR.distinct(shape6, seed, 0.0, 1.0).to(DEV)
-    V, _, I, J, K, L = shape6
-    c3 = c.reshape(V, I * J, K * L).contiguous()
-    return c, c3, c3.amax(2).contiguous(), c3.amax(1).contiguous()
-
-
-def mm_apply(shape6, mode):
-    """MutualMatching forward.  fp32 output: test_gpu_kernels.py::_mutual_matching_vs_fp64, relerr < 1e-5;
-    f16 straight / transposed outputs: test_gpu_f16.py::test_mm_nc_input_f16, rel. L2 < 1e-3; PAD mode:
-    test_gpu_fusion.py::test_mm_apply_padded_planes_equal_pad_passes, equal to the pad_planes passes."""
-    from ncnet_amd.ops.mutual import EPS
-    ref = _ref()
-    C = _ext_mod()
-    c, c3, rmax, cmax = _mm_inputs(shape6, 14)
-    V, R, Cc = c3.shape
-    I, J = shape6[2], shape6[3]
-    out = _nan(c3.shape)
-    outs = {"out": out}
-    if mode == "plain":
-        C.mm_apply(c3, rmax, cmax, out, None, None, EPS)
-    elif mode == "f16t":
-        outs["x"], outs["xt"] = _nan((V, R, Cc), torch.float16), _nan((V, Cc, R), torch.float16)
-        C.mm_apply(c3, rmax, cmax, out, outs["x"], outs["xt"], EPS)
-    else:
-        _, ppl = C.pad_geom(I, J, 5)
-        planes = _nan((2 * V * R, ppl), torch.bfloat16)
-        C.mm_apply(c3, rmax, cmax, out, planes[:V * R], planes[V * R:], EPS, [5, I, J])
-        outs["planes"] = planes
-
-    def check():
-        m = ref.mutual_matching(c.double()).reshape(V, R, Cc)
-        _finite(out)
-        assert relerr(out, m) < 1e-5
-        if mode == "f16t":
-            assert rel_l2(outs["x"], m) < 1e-3 and rel_l2(outs["xt"], m.transpose(1, 2)) < 1e-3
-        if mode == "pad":
-            want = torch.cat((_pad_1ch(out, I, J, 5), _pad_1ch(out, I, J, 5, 1, I, J)))
-            assert torch.equal(outs["planes"], want)
-    return outs, check
-
-
-def mm_bwd(shape6, one_pass):
-    """MutualMatching backward, one pass (mm_bwd_sums2d) or the separate row / column kernels.
-    test_gpu_kernels.py::_mutual_matching_vs_fp64: fp64 autograd, relerr < 1e-4."""
-    from ncnet_amd.ops.mutual import EPS
-    ref = _ref()
-    C = _ext_mod()
-    c, c3, rmax, cmax = _mm_inputs(shape6, 14)
-    rarg, carg = c3.argmax(2).int().contiguous(), c3.argmax(1).int().contiguous()
-    g = torch.randn(c.shape, generator=torch.Generator().manual_seed(15)).to(DEV)
-    gc = _nan(c3.shape)
-    C.mm_bwd(c3, g.reshape(c3.shape).contiguous(), rmax, rarg, cmax, carg, gc, EPS, one_pass)
-
-    def check():
-        cr = c.double().requires_grad_(True)
-        ref.mutual_matching(cr).backward(g.double())
-        _finite(gc)
-        assert relerr(gc.reshape(c.shape), cr.grad) < 1e-4
-    return {"gc": gc}, check
-
 
 for _shape6 in ((2, 1, 7, 10, 13, 20), (2, 1, 7, 11, 1, 263)):        # [V, R, C] = (2, 70, 260) and (2, 77, 263)
     _s = f"2x{_shape6[2] * _shape6[3]}x{_shape6[4] * _shape6[5]}"

@@ -3,6 +3,10 @@
 Inputs are rounded to bf16 first and the oracle runs in fp64 on those values,
 so the remaining differences are fp32 accumulation order and the bf16 rounding
 of stored activations.
+
+Where a kernel also has a case in the LDS poison table, its inputs, launch,
+oracle and bound are one recipe in tests/kernel_cases.py (``KC``) that both
+call; the test keeps only what it asserts beyond the recipe.
 """
 import os
 import pytest
@@ -10,25 +14,11 @@ import torch
 
 from ncnet_amd.ops import _ext
 from ncnet_amd.ops import reference as ref
+from tests import kernel_cases as KC
+from tests.kernel_cases import bf, rel_l2, relerr
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def bf(x):
-    return x.to(torch.bfloat16).double()
-
-
-def relerr(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
-
-
-def rel_l2(a, b):
-    """||a - b|| / ||b||: robust to the few ReLU-mask flips that bf16 activations
-    cause in a multi-layer composite (a flip moves one element by its full value)."""
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def test_extension_loaded():
@@ -63,33 +53,21 @@ def test_conv16v4_matches_v3_bitwise(epi, shape, monkeypatch, tune):
     accumulates every output in conv16v3's order: bit-identical outputs for the
     forward (bias + ReLU) and data-gradient (ReLU-mask) epilogues, including
     partial (k, l) tiles and j-blocks, and against the fp64 oracle."""
-    from ncnet_amd.ops.packing import pack_w16
-    torch.manual_seed(1)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    w_std = torch.randn(16, 16, 5, 5, 5, 5, device=DEV) * 0.05
-    w = pack_w16(w_std)
-    b = torch.randn(16, device=DEV) * 0.1
-    outs = []
-    for v3 in ("0", "1"):
-        tune("conv_v3", v3)
-        y = torch.full_like(x, float("nan"))
-        _ext.ext().conv16_fwd(x, w, b if epi == 1 else None, m if epi == 2 else None, y, 5, epi)
-        outs.append(y)
-    assert torch.isfinite(outs[0].float()).all()
-    assert torch.equal(outs[0], outs[1])
+    runs = _conv16_fwd_v4_and_v3(tune, 5, epi, shape, 1)
+    assert torch.equal(runs[0][0]["y"], runs[1][0]["y"])
     # and v4 itself against the fp64 oracle on the same bf16 operands: bias +
     # ReLU (forward) or the ReLU mask of the previous activation (the data
     # gradient's EPI_MASK epilogue)
-    z = ref.conv4d(x.double().permute(0, 5, 1, 2, 3, 4), ref.conv4d_weight_from_std(bf(w_std)), None)
-    if epi == 1:
-        want = torch.relu(z + b.double().view(1, 16, 1, 1, 1, 1))
-    else:
-        want = z * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-    got = outs[0].permute(0, 5, 1, 2, 3, 4)
-    # the only difference is the final bf16 rounding of the stored output (2^-9)
-    assert relerr(got, want) < 4e-3, relerr(got, want)
+    runs[0][1]()
+
+
+def _conv16_fwd_v4_and_v3(tune, ks, epi, shape, seed):
+    """The conv16_fwd recipe on the same inputs under conv_v3 0 (conv16v4) and 1 (conv16v3)."""
+    runs = []
+    for v3 in ("0", "1"):
+        tune("conv_v3", v3)
+        runs.append(KC.conv16_fwd(ks, epi, shape, seed))
+    return runs
 
 
 @pytest.mark.parametrize("ks,T", [(5, 20), (5, 15), (3, 25), (3, 20), (3, 15), (5, 30), (3, 30)])
@@ -99,27 +77,10 @@ def test_conv16v4_other_planes(ks, T, epi, tune):
     240 / 480 -- the 30 x 30 plane as two 30 x 15 tiles -- and k = 3):
     bit-identical to the general conv16v3 at the same tiles and within the
     final bf16 rounding of the fp64 oracle."""
-    from ncnet_amd.ops.packing import pack_w16
-    torch.manual_seed(2)
-    V, I, J = 2, 7, 11
-    x = torch.rand(V, I, J, T, T, 16, device=DEV).to(torch.bfloat16)
-    m = torch.randn(V, I, J, T, T, 16, device=DEV).to(torch.bfloat16)
-    w_std = torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05
-    w = pack_w16(w_std)
-    b = torch.randn(16, device=DEV) * 0.1
-    outs = []
-    for v3 in ("0", "1"):
-        tune("conv_v3", v3)
-        y = torch.full_like(x, float("nan"))
-        _ext.ext().conv16_fwd(x, w, b if epi == 1 else None, m if epi == 2 else None, y, ks, epi)
-        outs.append(y)
-    assert torch.isfinite(outs[0].float()).all()
-    z = ref.conv4d(x.double().permute(0, 5, 1, 2, 3, 4), ref.conv4d_weight_from_std(bf(w_std)), None)
-    want = torch.relu(z + b.double().view(1, 16, 1, 1, 1, 1)) if epi == 1 else z * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-    e4, e3 = relerr(outs[0].permute(0, 5, 1, 2, 3, 4), want), relerr(outs[1].permute(0, 5, 1, 2, 3, 4), want)
-    print(f"conv16v4 k{ks} {T}x{T}: v4 {e4:.2e} v3 {e3:.2e} bitwise {torch.equal(outs[0], outs[1])}")
-    assert e4 < 4e-3 and e3 < 4e-3, (e4, e3)
-    assert torch.equal(outs[0], outs[1])
+    runs = _conv16_fwd_v4_and_v3(tune, ks, epi, (2, 7, 11, T, T), 2)
+    for _, check in runs:
+        check()
+    assert torch.equal(runs[0][0]["y"], runs[1][0]["y"])
 
 
 @pytest.mark.parametrize("ks,T", [(5, 20), (5, 15), (3, 25), (3, 20), (3, 15), (5, 30), (3, 30)])
@@ -154,21 +115,8 @@ def test_conv16_blk_fwd(ks, shape, cin, relu):
     """Cout=1 conv in output-plane-block mode (4x4 output planes per
     workgroup = the 16 MFMA rows, partial blocks at the I/J edges, multi-tile
     K, L) vs the fp64 Conv4d oracle."""
-    from ncnet_amd.ops.packing import blk_out_weights, pack_w16_planes
-    torch.manual_seed(1)
-    V, I, J, K, L = shape
-    x = torch.rand(V, cin, I, J, K, L, device=DEV)
-    w = torch.randn(1, cin, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(1, device=DEV) * 0.1 - (0.3 if relu else 0.0)
-    xcl = torch.zeros(V, I, J, K, L, 16, device=DEV, dtype=torch.bfloat16)
-    xcl[..., :cin] = x.permute(0, 2, 3, 4, 5, 1).to(torch.bfloat16)
-    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
-    _ext.ext().conv16_blk_fwd(xcl, pack_w16_planes(blk_out_weights(w)), b, y, ks, relu)
-    yr = ref.conv4d(bf(x), ref.conv4d_weight_from_std(bf(w)), b.double())[:, 0]
-    if relu:
-        yr = torch.relu(yr)
-    assert torch.isfinite(y).all()
-    assert relerr(y, yr) < 1e-4
+    _, check = KC.conv16_blk_fwd(ks, shape, cin, relu)
+    check()
 
 
 @pytest.mark.parametrize("shape,cin,relu", [((3, 25, 25, 25, 25), 16, 1), ((2, 25, 25, 25, 25), 16, 0),
@@ -180,22 +128,9 @@ def test_cout1_taps_fwd(shape, cin, relu):
     LDS) vs the fp64 Conv4d oracle on the same bf16 operands, and bit for bit
     across two launches; a one-tap weight perturbation must be detected."""
     from ncnet_amd.ops.packing import cout1_taps_weights
-    torch.manual_seed(3)
-    ks = 5
-    V, I, J, K, L = shape
-    x = torch.rand(V, cin, I, J, K, L, device=DEV)
-    w = torch.randn(1, cin, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(1, device=DEV) * 0.1 - (0.3 if relu else 0.0)
-    xcl = torch.zeros(V, I, J, K, L, 16, device=DEV, dtype=torch.bfloat16)
-    xcl[..., :cin] = x.permute(0, 2, 3, 4, 5, 1).to(torch.bfloat16)
-    wt = cout1_taps_weights(w).to(torch.bfloat16)
-    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
-    assert _ext.ext().cout1_taps_fwd(xcl, wt, b, y, ks, relu)
-    yr = ref.conv4d(bf(x), ref.conv4d_weight_from_std(bf(w)), b.double())[:, 0]
-    if relu:
-        yr = torch.relu(yr)
-    assert torch.isfinite(y).all()
-    assert relerr(y, yr) < 1e-4, relerr(y, yr)
+    outs, check = KC.cout1_taps_fwd(shape, cin, relu)
+    c = check()
+    ks, y, xcl, w, wt, b, yr = 5, outs["y"], c["xcl"], c["w"], c["wt"], c["b"], c["yr"]
     y2 = torch.full_like(y, float("nan"))
     _ext.ext().cout1_taps_fwd(xcl, wt, b, y2, ks, relu)
     assert torch.equal(y, y2)
@@ -220,25 +155,8 @@ def test_cout1_taps_fwd(shape, cin, relu):
 def test_wgrad16p(ks, shape, nx, ng):
     """Double-buffered plane-only weight gradient (both ij groups per launch)
     vs the fp64 plane-conv definition: dW[tap][ci][co] = sum X[vox + tap] G[vox]."""
-    import torch.nn.functional as F
-    torch.manual_seed(2)
-    V, I, J, K, L = shape
-    x = (torch.rand((nx,) + shape + (16,), device=DEV) - 0.3).to(torch.bfloat16)
-    g = torch.randn((ng,) + shape + (16,), device=DEV).to(torch.bfloat16)
-    part = torch.full((64, nx * ng, ks * ks, 16, 16), float("nan"), device=DEV)
-    partb = torch.full((64, nx * ng, 16), float("nan"), device=DEV)
-    _ext.ext().wgrad16p(x, g, part, partb, ks)
-    s, sb = part.sum(0), partb.sum(0)
-    for a in range(nx):
-        for n in range(ng):
-            xx = x[a].double().reshape(V * I * J, K, L, 16).permute(0, 3, 1, 2)
-            gg = g[n].double().reshape(V * I * J, K, L, 16).permute(0, 3, 1, 2)
-            P = ks // 2
-            xp = F.pad(xx, (P, P, P, P))
-            want = torch.stack([torch.einsum("nckl,nokl->co", xp[:, :, dk:dk + K, dl:dl + L], gg)
-                                for dk in range(ks) for dl in range(ks)])   # [tap, ci, co]
-            assert relerr(s[a * ng + n], want) < 1e-4
-            assert relerr(sb[a * ng + n], gg.sum(dim=(0, 2, 3))) < 1e-4
+    _, check = KC.wgrad16p(ks, shape, nx, ng)
+    check()
 
 
 @pytest.mark.parametrize("cin,cout,ks", [(16, 16, 5), (1, 16, 5), (16, 1, 5), (16, 16, 3), (1, 16, 3), (16, 1, 3),
@@ -527,32 +445,10 @@ def test_wgrad16_kernel(variant, ks, shape):
     modes, vs autograd of the fp64 oracle."""
     import importlib
     nc = importlib.import_module("ncnet_amd.ops.nc.layers")
-    C = _ext.ext()
-    torch.manual_seed(11)
-    V, I, J, K, L = shape
     if variant == 3 and not nc.wgrad_v3_ok(shape, ks):
         pytest.skip("wgrad16v3 needs KS 3/5 and L + KS - 1 <= 32")
-    x = torch.rand(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    g = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    xr = x.double().permute(0, 5, 1, 2, 3, 4)
-    wr = torch.zeros(ks, 16, 16, ks, ks, ks, device=DEV, dtype=torch.float64, requires_grad=True)
-    yr = ref.conv4d(xr, wr, None)
-    (yr * g.double().permute(0, 5, 1, 2, 3, 4)).sum().backward()
-    dstd = ref.conv4d_weight_to_std(wr.grad)           # [co, ci, di, dj, dk, dl]
-    if variant == 3:
-        ng = nc.wgrad_v3_groups(shape, ks)
-    else:
-        ng = nc.wgrad_groups(ks, nc._nitems(shape))
-    part = torch.empty((2 * ng, ks * ks, ks * ks, 16, 16), device=DEV)
-    partb = torch.empty((2 * ng, 16), device=DEV)
-    C.wgrad16(x, g, part, partb, ks, 0, variant)
-    dw = nc._reduce_wgrad16(part.sum(0), ks, 16, 16)
-    assert relerr(dw, dstd) < 1e-3
-    assert relerr(partb.sum(0), g.double().sum(dim=(0, 1, 2, 3, 4))) < 1e-3
-    sp, sbp = nc.wgrad16_partials(C, x, g, ks, True)     # plane-only: the (P, P) offset
-    P = ks // 2
-    assert relerr(sp[0].permute(2, 1, 0).reshape(16, 16, ks, ks), dstd[:, :, P, P]) < 1e-3
-    assert relerr(sbp, partb.sum(0)) < 1e-5
+    _, check = KC.wgrad16(variant, ks, shape)
+    check()
 
 
 @pytest.mark.parametrize("flags", ["0", "1"])
@@ -639,34 +535,8 @@ def test_conv16_fwd_v2_epilogues(ks, epi, grp):
     output j-tiles per workgroup), on 7 x 9 planes (63 voxels, no multiple of 16) vs
     fp64 math on the same bf16 operands; the bounds of test_conv16_fwd (bf16 output)
     and test_conv16_fp8_kernel (planar fp32)."""
-    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
-    torch.manual_seed(4)
-    V, I, J, K, L = 1, 2, 6, 7, 9
-    if grp:
-        x = torch.rand(grp, V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-        w = (torch.randn(grp, 16, 16, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-        wp = pack_w16_planes(w)
-        xx = x.double().permute(0, 1, 2, 3, 6, 4, 5).reshape(grp, V * I * J, 16, K, L)
-        yr = sum(torch.nn.functional.conv2d(xx[g], w[g].double(), padding=ks // 2) for g in range(grp))
-        yr = yr.reshape(V, I, J, 16, K, L).permute(0, 3, 1, 2, 4, 5)          # [V, 16, I, J, K, L]
-    else:
-        xs = torch.rand(V, 16, I, J, K, L, device=DEV)
-        x = xs.permute(0, 2, 3, 4, 5, 1).contiguous().to(torch.bfloat16)
-        w = torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05
-        wp = pack_w16(w)
-        yr = ref.conv4d(bf(xs), ref.conv4d_weight_from_std(bf(w)), None)
-    m = None
-    if epi == 2:
-        m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-        yr = yr * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-    if epi == 4:
-        y = torch.full((16, V, I, J, K, L), float("nan"), device=DEV)
-        _ext.ext().conv16_fwd(x, wp.to(torch.bfloat16), None, None, y, ks, 4)
-        assert relerr(y.permute(1, 0, 2, 3, 4, 5), yr) < 1e-4
-    else:
-        y = torch.full((V, I, J, K, L, 16), float("nan"), device=DEV).to(torch.bfloat16)
-        _ext.ext().conv16_fwd(x, wp.to(torch.bfloat16), None, m, y, ks, epi)
-        assert relerr(y.permute(0, 5, 1, 2, 3, 4), yr) < 1e-2
+    _, check = KC.conv16_fwd_group_planes(ks, epi, (1, 2, 6, 7, 9), grp)
+    check()
 
 
 def test_bias_act_kernel():
@@ -787,34 +657,11 @@ def test_immatchnet_fp8_correlation_path():
 def test_conv16_fp8_kernel(ks, shape):
     """fp8 (OCP e4m3) inference conv16 vs fp64 math on the same fp8 values:
     bias+ReLU -> fp8 output and planar fp32 output, plain and group-plane mode."""
-    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
-    C = _ext.ext()
-    F8 = torch.float8_e4m3fn
-    torch.manual_seed(21)
-    V, I, J, K, L = shape
-    x = (torch.rand(V, I, J, K, L, 16, device=DEV) * 2).to(F8)
-    w = (torch.randn(16, 16, ks, ks, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-    wsc = 64.0
-    wq = (pack_w16(w).float() * wsc).to(F8)
-    wr = (w * wsc).to(F8).double() / wsc          # the exact fp8 weight values used
-    b = torch.randn(16, device=DEV) * 0.1
-    xr = x.double().permute(0, 5, 1, 2, 3, 4)
-    yr = ref.conv4d(xr, ref.conv4d_weight_from_std(wr), b.double())
-    y = torch.empty((V, I, J, K, L, 16), dtype=F8, device=DEV)
-    C.conv16f8_fwd(x, wq, b, y, ks, 1, 1.0 / wsc)
-    y_ref = torch.relu(yr).permute(0, 2, 3, 4, 5, 1)
-    assert rel_l2(y.float(), y_ref) < 0.04          # e4m3 output rounding (3 mantissa bits)
+    _, check = KC.conv16f8_fwd(ks, shape, 0)
+    check()
     # planar fp32, group-plane mode with 2 groups at the (i, j) plane
-    wp = (torch.randn(2, 16, 16, ks, ks, device=DEV) * 0.05).to(torch.bfloat16).float()
-    wpq = (pack_w16_planes(wp).float() * wsc).to(F8)
-    wpr = (wp * wsc).to(F8).double() / wsc
-    x2 = (torch.rand(2, V, I, J, K, L, 16, device=DEV) * 2).to(F8)
-    z = torch.empty((16, V, I, J, K, L), dtype=torch.float32, device=DEV)
-    C.conv16f8_fwd(x2, wpq, None, z, ks, 4, 1.0 / wsc)
-    xx = x2.double().permute(0, 1, 2, 3, 6, 4, 5).reshape(2, V * I * J, 16, K, L)
-    zr = sum(torch.nn.functional.conv2d(xx[g], wpr[g], padding=ks // 2) for g in range(2))
-    zr = zr.reshape(V, I, J, 16, K, L).permute(3, 0, 1, 2, 4, 5)
-    assert relerr(z, zr) < 1e-4
+    _, check = KC.conv16f8_fwd(ks, shape, 2)
+    check()
 
 
 def test_immatchnet_fp8_nc_path(runtime):
@@ -914,22 +761,7 @@ def test_conv2d_nhwc_dma_ring_small_tiles(cout, shape, tune):
 
 
 def _conv2d_nhwc_vs_fp64(cin, cout, k, stride, pad, res, relu, shape):
-    C = _ext.ext()
-    torch.manual_seed(17)
-    cl = torch.channels_last
-    x = torch.randn(shape[0], cin, shape[1], shape[2], device=DEV).to(torch.bfloat16).contiguous(memory_format=cl)
-    w = (torch.randn(cout, cin, k, k, device=DEV) * 0.05).to(torch.bfloat16).contiguous(memory_format=cl)
-    b = torch.randn(cout, device=DEV)
-    yr = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), stride, pad)
-    r = None
-    if res:
-        r = torch.randn(yr.shape, device=DEV).to(torch.bfloat16).contiguous(memory_format=cl)
-        yr = yr + r.double()
-    if relu:
-        yr = torch.relu(yr)
-    y = torch.full(yr.shape, float("nan"), dtype=torch.bfloat16, device=DEV).contiguous(memory_format=cl)
-    C.conv2d_nhwc(x, w, b, r, y, stride, pad, 1 if relu else 0)
-    assert relerr(y, yr) < 1e-2
+    KC.conv2d_nhwc(cin, cout, k, stride, pad, res, relu, shape, torch.bfloat16, 17)[1]()
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,pad,res,relu,shape", [
@@ -941,23 +773,8 @@ def test_conv2d_nhwc_256x256_tile(cin, cout, k, stride, pad, res, relu, shape, t
     """The 256 x 256 DMA-ring tile of the Cout = 256 trunk convs (conv2d_nhwc_v2
     <256, 256>, forced by conv2d_variant 4) vs F.conv2d in fp64 on bf16 inputs."""
     tune("conv2d_variant", 4)
-    C = _ext.ext()
-    torch.manual_seed(23)
-    cl = torch.channels_last
-    x = torch.randn(shape[0], cin, shape[1], shape[2], device=DEV).to(torch.bfloat16).contiguous(memory_format=cl)
-    w = (torch.randn(cout, cin, k, k, device=DEV) * 0.05).to(torch.bfloat16).contiguous(memory_format=cl)
-    b = torch.randn(cout, device=DEV)
-    yr = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), stride, pad)
-    r = None
-    if res:
-        r = torch.randn(yr.shape, device=DEV).to(torch.bfloat16).contiguous(memory_format=cl)
-        yr = yr + r.double()
-    if relu:
-        yr = torch.relu(yr)
-    y = torch.full(yr.shape, float("nan"), dtype=torch.bfloat16, device=DEV).contiguous(memory_format=cl)
-    C.conv2d_nhwc(x, w, b, r, y, stride, pad, 1 if relu else 0)
-    assert torch.isfinite(y).all()
-    assert relerr(y, yr) < 1e-2
+    _, check = KC.conv2d_nhwc(cin, cout, k, stride, pad, res, relu, shape, torch.bfloat16, 23)
+    check()
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,pad,res,relu,shape,dt", [
@@ -977,24 +794,9 @@ def test_conv2d_nhwc_v3(cin, cout, k, stride, pad, res, relu, shape, dt, tune):
     """conv2d_nhwc_v3 (one round of chip-sized workgroups: 16 TM x 64 TN tiles,
     8 waves as 2 K-groups x 4 N-groups, LDS-DMA ring, K-group sum in the
     epilogue) vs F.conv2d in fp64 on 16-bit inputs: ragged M, stride 2, residual."""
-    C = _ext.ext()
     tune("conv2d_variant", "3")
-    torch.manual_seed(18)
-    cl = torch.channels_last
-    x = torch.randn(shape[0], cin, shape[1], shape[2], device=DEV).to(dt).contiguous(memory_format=cl)
-    w = (torch.randn(cout, cin, k, k, device=DEV) * 0.05).to(dt).contiguous(memory_format=cl)
-    b = torch.randn(cout, device=DEV)
-    yr = torch.nn.functional.conv2d(x.double(), w.double(), b.double(), stride, pad)
-    r = None
-    if res:
-        r = torch.randn(yr.shape, device=DEV).to(dt).contiguous(memory_format=cl)
-        yr = yr + r.double()
-    if relu:
-        yr = torch.relu(yr)
-    y = torch.full(yr.shape, float("nan"), dtype=dt, device=DEV).contiguous(memory_format=cl)
-    C.conv2d_nhwc(x, w, b, r, y, stride, pad, 1 if relu else 0)
-    assert torch.isfinite(y.float()).all()
-    assert relerr(y, yr) < 1e-2, relerr(y, yr)
+    _, check = KC.conv2d_nhwc(cin, cout, k, stride, pad, res, relu, shape, dt, 18)
+    check()
 
 
 @pytest.mark.parametrize("ks,shape", [(5, (2, 6, 7, 25, 25)), (3, (1, 4, 9, 30, 27)), (5, (1, 3, 12, 9, 7))])
@@ -1150,24 +952,8 @@ def test_nc_fused_k3_vs_quantized_oracle(cfg):
     x0, the weights and the hidden activation; cfg = (R, IR, TK, TL) forces
     multi-workgroup splits along j, i and the (k, l) tile (None: the
     production choice, fused_tiles)."""
-    import importlib
-    from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
-    torch.manual_seed(21)
-    V, I, J, K, L = 2, 9, 13, 11, 14
-    w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
-    w2 = torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.1
-    b1, b2 = torch.rand(16, device=DEV) * 0.1 - 0.03, torch.rand(1, device=DEV) * 0.1
-    ws = [ref.conv4d_weight_from_std(w1), ref.conv4d_weight_from_std(w2)]
-    x0 = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    wts = nc._fused_weights(ws, [b1, b2])
-    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
-    tk, tl, R, IR = nc.fused_tiles(V, I, J, K, L) if cfg is None else (cfg[2], cfg[3], cfg[0], cfg[1])
-    _ext.ext().nc_fused_k3(x0, *wts, y, R, IR, tk, tl)
-    torch.cuda.synchronize()
-    assert torch.isfinite(y).all()
-    yr = qo.nc_stack(x0.double().unsqueeze(1), [w1.double(), w2.double()], [b1.double(), b2.double()])
-    assert relerr(y, yr.squeeze(1)) < 2e-3
+    _, check = KC.nc_fused_k3((2, 9, 13, 11, 14), cfg, 21)
+    check()
 
 
 @pytest.mark.parametrize("shape", [(1, 7500, 7500), (3, 625, 400), (2, 130, 1852), (1, 64, 256), (4, 625, 625),
@@ -1254,22 +1040,8 @@ def test_nc_fused_k3_one_wide_workgroup():
     """The > 80 KB configuration of the fused NC kernel (a 24-plane output
     ring: one 16-wave workgroup per CU, csrc/nc_fused.hip NW = 16) against the
     quantized fp64 oracle."""
-    import importlib
-    from ncnet_amd.engine import quantized_oracle as qo
-    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
-    torch.manual_seed(23)
-    V, I, J, K, L = 1, 6, 26, 17, 22
-    w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
-    w2 = torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.1
-    b1, b2 = torch.rand(16, device=DEV) * 0.1 - 0.03, torch.rand(1, device=DEV) * 0.1
-    x0 = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    wts = nc._fused_weights([ref.conv4d_weight_from_std(w1), ref.conv4d_weight_from_std(w2)], [b1, b2])
-    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
-    _ext.ext().nc_fused_k3(x0, *wts, y, 24, 4, 15, 20)      # R = 24, IR = 4, 15 x 20 tiles
-    torch.cuda.synchronize()
-    assert torch.isfinite(y).all()
-    yr = qo.nc_stack(x0.double().unsqueeze(1), [w1.double(), w2.double()], [b1.double(), b2.double()])
-    assert relerr(y, yr.squeeze(1)) < 2e-3
+    _, check = KC.nc_fused_k3((1, 6, 26, 17, 22), (24, 4, 15, 20), 23)      # R = 24, IR = 4, 15 x 20 tiles
+    check()
 
 
 @pytest.mark.parametrize("tiles", [(8, 4, 8, 8), (10, 4, 15, 20), (24, 4, 15, 20)])
@@ -1323,11 +1095,6 @@ def test_neigh_consensus_fused_symmetric_wrapper():
     assert relerr(y, yr) < 2e-3
 
 
-def _f8q(t, s):
-    """OCP e4m3 rounding at the power-of-two scale s (values returned unscaled, fp64)."""
-    return (t.double() * s).float().clamp(-448, 448).to(torch.float8_e4m3fn).double() / s
-
-
 @pytest.mark.parametrize("cfg", [None, (3, 4, 6, 7), (10, 4, 15, 20), (8, 3, 19, 17), (5, 2, 9, 11)])
 def test_nc_fused_k3_f8_vs_quantized_oracle(cfg):
     """The e4m3 fused NC kernel (csrc/nc_fused.hip nc_fused_k3_f8: one MX
@@ -1337,45 +1104,12 @@ def test_nc_fused_k3_f8_vs_quantized_oracle(cfg):
     channel map shows as an O(1) error, the fp8 quantisation itself cancels.
     cfg = (R, IR, TK, TL); the 3200 px (15 x 20, R 10) and 1600 px (19 x 17,
     R 8) tiles are the compile-time instantiations."""
-    import importlib
-    nc = importlib.import_module("ncnet_amd.ops.nc.fused")
-    torch.manual_seed(41)
-    V, I, J, K, L = 2, 9, 13, 11, 14
-    w1 = torch.randn(16, 1, 3, 3, 3, 3, device=DEV) * 0.2
-    w2 = torch.randn(1, 16, 3, 3, 3, 3, device=DEV) * 0.1
-    b1, b2 = torch.rand(16, device=DEV) * 0.1 - 0.03, torch.rand(1, device=DEV) * 0.1
-    ws = [ref.conv4d_weight_from_std(w1), ref.conv4d_weight_from_std(w2)]
-    # MutualMatching-like input: [0, 1], most entries small
-    x0 = (torch.rand(V, I, J, K, L, device=DEV) ** 3).to(torch.bfloat16)
-    tens, (sx, inv1, sh, inv2) = nc._fused_weights_f8_build(ws, [b1, b2])
-    sw1, sw2 = 1.0 / (inv1 * sx), 1.0 / (inv2 * sh)
-    y = torch.full((V, I, J, K, L), float("nan"), device=DEV)
-    tk, tl, R, IR = nc.fused_tiles(V, I, J, K, L) if cfg is None else (cfg[2], cfg[3], cfg[0], cfg[1])
-    _ext.ext().nc_fused_k3_f8(x0, *tens, y, R, IR, tk, tl, sx, inv1, sh, inv2)
-    torch.cuda.synchronize()
-    assert torch.isfinite(y).all()
-    xq = _f8q(x0, sx).unsqueeze(1)
-    h = torch.relu(ref.conv4d(xq, ref.conv4d_weight_from_std(_f8q(w1, sw1))) + b1.double().view(1, -1, 1, 1, 1, 1))
-    h = _f8q(h, sh)
-    yr = torch.relu(ref.conv4d(h, ref.conv4d_weight_from_std(_f8q(w2, sw2))) + b2.double().view(1, -1, 1, 1, 1, 1))
-    # (a hidden value on the other side of an e4m3 rounding boundary in fp32
-    # vs fp64 moves by one e4m3 ulp, 6 %: a few such flips, not O(1) errors)
-    assert relerr(y, yr.squeeze(1)) < 2e-2 and rel_l2(y, yr.squeeze(1)) < 2e-3
+    outs, check = KC.nc_fused_k3_f8((2, 9, 13, 11, 14), cfg)
+    c = check()
     # and the unquantised fp64 stack: the e4m3 error of the whole NC
-    yf = ref.neigh_consensus(x0.double().unsqueeze(1), [w.double() for w in ws], [b1.double(), b2.double()],
+    yf = ref.neigh_consensus(c["x0"].double().unsqueeze(1), [w.double() for w in c["ws"]], [b.double() for b in c["bs"]],
                              symmetric=False)
-    assert rel_l2(y, yf.squeeze(1)) < 0.05
-
-
-def _pad_1ch(x5, ks, trans=False):
-    """x5 [V, I, J, K, L] (any float dtype) -> padded bf16 planes via pad_planes."""
-    V, I, J, K, L = x5.shape
-    C = _ext.ext()
-    lp, ppl = C.pad_geom(K, L, ks) if not trans else C.pad_geom(I, J, ks)
-    n = V * (K * L if trans else I * J)
-    y = torch.zeros((n, ppl), dtype=torch.bfloat16, device=DEV)
-    C.pad_planes(x5.reshape(V, I * J, K * L).contiguous(), y, *((I, J) if trans else (K, L)), ks, 1 if trans else 0)
-    return y
+    assert rel_l2(outs["y"], yf.squeeze(1)) < 0.05
 
 
 @pytest.mark.parametrize("ks,shape", [(5, (2, 25, 25, 25, 25)), (5, (1, 6, 7, 25, 25)), (5, (1, 3, 11, 25, 25)),
@@ -1387,7 +1121,8 @@ def test_conv1x16_vs_oracle(ks, shape, epi):
     gathered by ds_read_b64_tr_b16 from 4 element-shifted LDS copies of each
     plane) vs the fp64 oracle: bias + ReLU forward, and the ReLU-mask epilogue
     of the last layer's data gradient."""
-    _conv1x16_vs_oracle(ks, shape, epi)
+    _, check = KC.conv1x16(ks, shape, epi)
+    check()
 
 
 @pytest.mark.parametrize("pd", [1, 3])
@@ -1397,36 +1132,14 @@ def test_conv1x16_lookahead_variants(pd, epi, tune):
     (tuning switch c1x_pd; the default 2 runs everywhere else) on the same oracle and
     bound; J = 6 leaves the second block of 5 output j-planes partial."""
     tune("c1x_pd", pd)
-    _conv1x16_vs_oracle(5, (1, 2, 6, 25, 25), epi)
-
-
-def _conv1x16_vs_oracle(ks, shape, epi):
-    from ncnet_amd.ops.packing import pack_w1x
-    torch.manual_seed(3)
-    V, I, J, K, L = shape
-    x = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    w = torch.randn(16, 1, ks, ks, ks, ks, device=DEV) * 0.05
-    b = torch.randn(16, device=DEV) * 0.1
-    m = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    y = torch.full((V, I, J, K, L, 16), float("nan"), dtype=torch.bfloat16, device=DEV)
-    ran = _ext.ext().conv1x16(_pad_1ch(x, ks), pack_w1x(w), b if epi == 1 else None, m if epi == 2 else None, y, ks, epi)
-    assert ran
-    z = ref.conv4d(x.double().unsqueeze(1), ref.conv4d_weight_from_std(bf(w)), None)   # [V, 16, I, J, K, L]
-    if epi == 1:
-        want = torch.relu(z + b.double().view(1, 16, 1, 1, 1, 1))
-    else:
-        want = z * (m.double().permute(0, 5, 1, 2, 3, 4) > 0)
-    assert relerr(y.permute(0, 5, 1, 2, 3, 4), want) < 1e-2
+    _, check = KC.conv1x16(5, (1, 2, 6, 25, 25), epi)
+    check()
 
 
 def test_pad_planes_transposed():
     """pad_planes trans=1 writes the planes of the A<->B-swapped volume."""
-    torch.manual_seed(4)
-    V, I, J, K, L = 2, 9, 11, 9, 11
-    x = torch.randn(V, I, J, K, L, device=DEV)
-    a = _pad_1ch(x, 5, trans=True)
-    b = _pad_1ch(x.permute(0, 3, 4, 1, 2).contiguous(), 5)
-    assert torch.equal(a, b)
+    _, check = KC.pad_planes_transposed()
+    check()
 
 
 @pytest.mark.parametrize("ks,shape,G", [(5, (2, 25, 25, 25, 25), 256), (5, (1, 6, 7, 25, 25), 7),
@@ -1442,30 +1155,8 @@ def test_wgrad1x16_vs_oracle(ks, shape, G, bias):
     vs autograd of the fp64 oracle, for both uses: the first layer (D = output
     gradient, X1 = input: R = dW) and the Cout = 1 last layer (D = input,
     X1 = output gradient: dW = R with all four kernel axes flipped)."""
-    torch.manual_seed(21)
-    V, I, J, K, L = shape
-    x1 = torch.rand(V, I, J, K, L, device=DEV).to(torch.bfloat16)
-    d = torch.randn(V, I, J, K, L, 16, device=DEV).to(torch.bfloat16)
-    nt = ks * ks
-    part = torch.full((G, nt, 32, 16), float("nan"), device=DEV)
-    partb = torch.full((G, 16), float("nan"), device=DEV) if bias else None
-    assert _ext.ext().wgrad1x16(d, _pad_1ch(x1, ks), part, partb, ks)
-    R = part.sum(0)[:, :nt, :]                                   # [tap, combo, c]
-    # first layer: y[co] = conv(x1; W[co, 0]), dL/dy = d  ->  dW[co, 0, di, dj, dk, dl]
-    wr = torch.zeros(ks, 16, 1, ks, ks, ks, device=DEV, dtype=torch.float64, requires_grad=True)
-    yr = ref.conv4d(x1.double().unsqueeze(1), wr, None)
-    (yr * d.double().permute(0, 5, 1, 2, 3, 4)).sum().backward()
-    want = ref.conv4d_weight_to_std(wr.grad)[:, 0].reshape(16, nt, nt)      # [co, combo, tap]
-    assert relerr(R.permute(2, 1, 0), want) < 1e-4
-    # last layer: y = conv(d; W[0, ci]), dL/dy = x1  ->  dW[0, ci, t] = R[2P - t][ci]
-    w3 = torch.zeros(ks, 1, 16, ks, ks, ks, device=DEV, dtype=torch.float64, requires_grad=True)
-    y3 = ref.conv4d(d.double().permute(0, 5, 1, 2, 3, 4), w3, None)
-    (y3 * x1.double().unsqueeze(1)).sum().backward()
-    want3 = ref.conv4d_weight_to_std(w3.grad)[0]                               # [ci, di, dj, dk, dl]
-    got3 = R.permute(2, 1, 0).reshape(16, ks, ks, ks, ks).flip(1, 2, 3, 4)
-    assert relerr(got3, want3) < 1e-4
-    if bias:
-        assert relerr(partb.sum(0), d.double().sum(dim=(0, 1, 2, 3, 4))) < 1e-4
+    _, check = KC.wgrad1x16(ks, shape, G, bias)
+    check()
 
 
 @pytest.mark.parametrize("symmetric", [True, False])

@@ -7,6 +7,7 @@ import torch
 
 from ncnet_amd.ops import _ext
 from ncnet_amd.ops import reference as ref
+from tests import kernel_cases as KC
 
 pytestmark = pytest.mark.gpu
 
@@ -72,17 +73,13 @@ def test_x3_fused_matches_fp64(ks, ch, shape):
     assert max(errs.values()) < 2e-4, errs
 
 
-def _split(t):
-    hi = t.to(torch.bfloat16)
-    return hi, (t - hi.float()).to(torch.bfloat16)
-
-
 @pytest.mark.parametrize("grp,plane,epi", [(2, 25, 1), (2, 25, 2), (0, 25, 1), (0, 25, 2), (0, 9, 1), (0, 9, 2),
                                            (2, 9, 2)])
 def test_conv16_x3_kernel_vs_emulator(grp, plane, epi):
     """One conv16_fwd_x3 launch (group-plane or full (di, dj) sum; bias+ReLU or
     ReLU-mask epilogue) against the fp64 emulator: hi + lo to ~1e-5."""
-    _conv16_x3_vs_emulator(grp, plane, epi, 5, (2, 6, 5))
+    _, check = KC.conv16_fwd_x3(grp, plane, epi, 5, (2, 6, 5))
+    check()
 
 
 @pytest.mark.parametrize("ks,plane", [(5, 15), (3, 15), (3, 20), (3, 25), (3, 30)])
@@ -92,42 +89,8 @@ def test_conv16_x3_v4_planes_vs_emulator(ks, plane, epi):
     15 x 15 plane, KS 3 at all four compile-time planes (30 x 30: two 30 x 15
     tiles) -- on the same emulator oracle and bound; J = 6 leaves the second
     block of R = 5 output j-planes partial."""
-    _conv16_x3_vs_emulator(0, plane, epi, ks, (1, 2, 6))
-
-
-def _conv16_x3_vs_emulator(grp, plane, epi, ks, vij):
-    import sys, os
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-    from tests import emu_ext
-    torch.manual_seed(3)
-    V, I, J = vij
-    shp = (V, I, J, plane, plane)
-    xs = (grp,) if grp else ()
-    x = torch.randn(xs + shp + (16,), device="cuda")
-    xh, xl = _split(x)
-    from ncnet_amd.ops.packing import pack_w16, pack_w16_planes
-    if grp:
-        w = torch.randn(grp, 16, 16, ks, ks, device="cuda") * 0.05
-        pack = pack_w16_planes
-    else:
-        w = torch.randn(16, 16, ks, ks, ks, ks, device="cuda") * 0.05
-        pack = pack_w16
-    whi = w.to(torch.bfloat16).float()
-    wp2 = torch.stack((pack(whi), pack(w - whi))).contiguous()
-    bias = torch.rand(16, device="cuda") * 0.1 if epi == 1 else None
-    m = torch.randn(shp + (16,), device="cuda").to(torch.bfloat16) if epi == 2 else None
-    yh = torch.empty(shp + (16,), dtype=torch.bfloat16, device="cuda")
-    yl = torch.empty_like(yh)
-    _ext.ext().conv16_fwd_x3(xh, xl, wp2, bias, m, yh, yl, ks, epi)
-    eh = torch.empty(shp + (16,), dtype=torch.float64)
-    el = torch.empty_like(eh)
-    emu_ext.conv16_fwd_x3(xh.cpu(), xl.cpu(), wp2.cpu(), None if bias is None else bias.cpu(),
-                          None if m is None else m.cpu(), eh, el, ks, epi)
-    got = yh.double().cpu() + yl.double().cpu()
-    want = eh + el
-    err = rl2(got, want)
-    print("conv16_fwd_x3 error", err)
-    assert err < 2e-5, err
+    _, check = KC.conv16_fwd_x3(0, plane, epi, ks, (1, 2, 6))
+    check()
 
 
 def test_x3_fused_matches_per_conv_path():
@@ -157,18 +120,6 @@ def test_x3_fused_matches_per_conv_path():
     assert max(errs) < 1e-4, errs
 
 
-def _pairs(t_nhwc):
-    """fp32 [N, H, W, C] -> bf16 [N, H, W, 2C] = [hi | lo]."""
-    hi = t_nhwc.to(torch.bfloat16)
-    lo = (t_nhwc - hi.float()).to(torch.bfloat16)
-    return torch.cat((hi, lo), -1).contiguous()
-
-
-def _unpair(p):
-    c = p.shape[-1] // 2
-    return p[..., :c].double() + p[..., c:].double()
-
-
 @pytest.mark.parametrize("cin,cout,k,stride,pad,res,relu,shape", [
     (256, 256, 3, 1, 1, False, True, (3, 25, 25)), (1024, 256, 1, 1, 0, False, True, (2, 25, 25)),
     (256, 1024, 1, 1, 0, True, True, (2, 25, 25)), (64, 64, 3, 1, 1, False, True, (2, 37, 29)),
@@ -179,30 +130,8 @@ def _unpair(p):
 def test_conv2d_x3_vs_fp64(cin, cout, k, stride, pad, res, relu, shape):
     """conv2d_nhwc_v3 X3 mode: [hi | lo] bf16 pairs in and out, acc = X_hi W_hi +
     X_lo W_hi + X_hi W_lo, fp32 bias / residual / ReLU: the fp32 conv to ~1e-5."""
-    C = _ext.ext()
-    torch.manual_seed(5)
-    n, h, w = shape
-    x = torch.randn(n, h, w, cin, device="cuda")
-    wt = torch.randn(cout, cin, k, k, device="cuda") * (1.0 / (cin * k * k) ** 0.5)
-    b = torch.randn(cout, device="cuda") * 0.1
-    wcl = wt.permute(0, 2, 3, 1)
-    whi = wcl.to(torch.bfloat16)
-    w3 = torch.cat((whi, whi, (wcl - whi.float()).to(torch.bfloat16)), -1).contiguous()
-    xp = _pairs(x)
-    want = torch.nn.functional.conv2d(_unpair(xp).permute(0, 3, 1, 2), wt.double(), b.double(), stride, pad)
-    want = want.permute(0, 2, 3, 1)
-    r = None
-    if res:
-        rr = torch.randn(want.shape, device="cuda")
-        r = _pairs(rr)
-        want = want + _unpair(r)
-    if relu:
-        want = torch.relu(want)
-    y = torch.full(tuple(want.shape[:3]) + (2 * cout,), float("nan"), dtype=torch.bfloat16, device="cuda")
-    C.conv2d_nhwc_x3(xp, w3, b, r, y, stride, pad, 1 if relu else 0)
-    err = rl2(_unpair(y), want)
-    print("conv2d x3 error", err)
-    assert err < 3e-5, err
+    _, check = KC.conv2d_nhwc_x3(cin, cout, k, stride, pad, res, relu, shape)
+    check()
 
 
 def test_trunk_x3_plan_vs_fp64():
