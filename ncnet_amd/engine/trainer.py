@@ -1,6 +1,8 @@
 """Weakly-supervised training loop (train.py:110-205), DP-aware; optionally
 keypoint-supervised (``Trainer(loss='strong')``) or warp-supervised
-(``Trainer(loss='warp')``), both extensions beyond the reference.
+(``Trainer(loss='warp')``), both extensions beyond the reference.  The losses
+are rows of one table, ops/loss.py ``LOSSES``: ``train_step`` / ``eval_step``
+and ``loss_from_features`` read it and never branch on the loss's name.
 
 Differences from the reference, all semantics-preserving:
 * the negative pass reuses the positive-pass backbone features rolled by one
@@ -29,7 +31,7 @@ import torch
 
 from .. import config as _config
 
-from ..ops.loss import strong_loss_from_corr, warp_loss_from_corr, weak_loss_from_corr
+from ..ops.loss import LOSSES
 from ..parallel.dist import DistContext, GradBucket, all_reduce_mean
 from ..utils.timing import active as active_timer, segment
 
@@ -100,64 +102,56 @@ def make_adam(params, lr: float) -> torch.optim.Optimizer:
     return torch.optim.Adam(params, lr=lr, fused=True) if fused else torch.optim.Adam(params, lr=lr)
 
 
+def loss_from_features(model, feats, batch, loss: str, normalization: str | None = "softmax") -> torch.Tensor:
+    """Loss ``loss`` (a key of ops/loss.py LOSSES) on backbone features
+    ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
+    f, hw, b = feats
+    spec = LOSSES[loss]
+    return spec.from_corr(model.training_volumes(f, hw, b, spec.negatives), batch, normalization)
+
+
+def _batch_volumes(model, batch, negatives: bool):
+    """A batch's volumes, backbone included (models/immatchnet.py
+    training_volumes), and the relocalization pool's offsets (None without one)."""
+    src, tgt = batch["source_image"], batch["target_image"]
+    with segment("backbone"):
+        f, hw = model.extract(torch.cat((src, tgt), 0))
+    return model.training_volumes(f, hw, src.shape[0], negatives, return_delta=True)
+
+
+def _batch_loss(model, batch, loss: str, normalization: str | None = "softmax") -> torch.Tensor:
+    spec = LOSSES[loss]
+    return spec.from_corr(_batch_volumes(model, batch, spec.negatives)[0], batch, normalization)
+
+
 def weak_loss(model, batch, normalization: str | None = "softmax", alpha: float = 30) -> torch.Tensor:
     """score_neg - score_pos (train.py:110-156). ``alpha`` is unused, as in the reference."""
-    src, tgt = batch["source_image"], batch["target_image"]
-    vols = model.weak_loss_volumes(src, tgt)
-    return weak_loss_from_corr(vols, src.shape[0], normalization)
+    return _batch_loss(model, batch, "weak", normalization)
 
 
 def weak_loss_from_features(model, feats, normalization: str | None = "softmax") -> torch.Tensor:
     """weak_loss on backbone features ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
-    f, hw, b = feats
-    return weak_loss_from_corr(model.weak_loss_volumes_from_features(f, hw, b), b, normalization)
+    return loss_from_features(model, feats, None, "weak", normalization)
 
 
 def strong_loss(model, batch) -> torch.Tensor:
     """Keypoint-supervised loss (ops/reference.py keypoint_ce) of the positive
     pairs: the model's volume against the batch's ``source_points`` /
     ``target_points`` / ``*_im_size`` -- the fields eval/pck.py scores."""
-    return strong_loss_from_corr(_positive_volumes(model, batch), batch)
-
-
-def _positive_volumes(model, batch, return_delta: bool = False):
-    """The positive pairs' volumes [B,1,h,w,h,w] of a batch (backbone included);
-    ``return_delta``: also the relocalization pool's offsets (None without one)."""
-    src, tgt = batch["source_image"], batch["target_image"]
-    with segment("backbone"):
-        f, hw = model.extract(torch.cat((src, tgt), 0))
-    if return_delta:
-        return model.match_volumes_from_features(f, hw, src.shape[0], return_delta=True)
-    return model.match_volumes_from_features(f, hw, src.shape[0])
-
-
-def _reloc_k(model) -> int:
-    """The model's relocalization pool size when it pools (k > 1), else 1."""
-    k = int(getattr(model, "relocalization_k_size", 0) or 0)
-    return k if k > 1 else 1
-
-
-def strong_loss_from_features(model, feats, batch) -> torch.Tensor:
-    """strong_loss on backbone features ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
-    f, hw, b = feats
-    return strong_loss_from_corr(model.match_volumes_from_features(f, hw, b), batch)
+    return _batch_loss(model, batch, "strong")
 
 
 def warp_loss(model, batch) -> torch.Tensor:
     """Dense correspondence loss (ops/reference.py dense_ce) of a two-view
     batch (data/datasets.py gpu_view_batch): the model's positive volumes
     against the batch's ``warp_maps``."""
-    return warp_loss_from_corr(_positive_volumes(model, batch), batch)
+    return _batch_loss(model, batch, "warp")
 
 
-def warp_loss_from_features(model, feats, batch) -> torch.Tensor:
-    """warp_loss on backbone features ``(f, (h, w), b)`` from TrunkPrefetcher.take."""
-    f, hw, b = feats
-    return warp_loss_from_corr(model.match_volumes_from_features(f, hw, b), batch)
-
-
-_KEYPOINT_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size", "L_pck")
-_WARP_FIELDS = ("warp_maps",) + _KEYPOINT_FIELDS
+def _reloc_k(model) -> int:
+    """The model's relocalization pool size when it pools (k > 1), else 1."""
+    k = int(getattr(model, "relocalization_k_size", 0) or 0)
+    return k if k > 1 else 1
 
 
 def batch_pck(corr4d, batch, alpha: float = 0.1, delta4d=None, k_size: int = 1) -> torch.Tensor:
@@ -256,7 +250,7 @@ class Trainer:
 
     def __init__(self, model, optimizer, ctx: DistContext, normalization="softmax", nan_guard=True,
                  metrics_path: str | None = None, fault_step: int | None = None, loss: str = "weak"):
-        if loss not in ("weak", "strong", "warp"):
+        if loss not in LOSSES:
             raise ValueError(f"loss must be 'weak', 'strong' or 'warp', got {loss!r}")
         self.loss = loss
         self.model = model
@@ -310,22 +304,16 @@ class Trainer:
         with segment("forward"):
             feats = self.prefetch.take(batch)
             self.prefetch.submit(next_batch)
-            if self.loss in ("strong", "warp"):
-                if self.prefetch.enabled:
-                    # the keypoint tensors / view maps were moved on the prefetch stream with the
-                    # images (to_device); take() made the main stream wait for it, and like the
-                    # features they must not be recycled there while this step reads them
-                    main = torch.cuda.current_stream(self.prefetch.stream.device)
-                    for k in _WARP_FIELDS if self.loss == "warp" else _KEYPOINT_FIELDS:
-                        v = batch.get(k)
-                        if torch.is_tensor(v) and v.is_cuda:
-                            v.record_stream(main)
-                if self.loss == "warp":
-                    loss = warp_loss_from_features(self.model, feats, batch)
-                else:
-                    loss = strong_loss_from_features(self.model, feats, batch)
-            else:
-                loss = weak_loss_from_features(self.model, feats, self.normalization)
+            if self.prefetch.enabled:
+                # the keypoint tensors / view maps were moved on the prefetch stream with the
+                # images (to_device); take() made the main stream wait for it, and like the
+                # features they must not be recycled there while this step reads them
+                main = torch.cuda.current_stream(self.prefetch.stream.device)
+                for k in LOSSES[self.loss].fields:
+                    v = batch.get(k)
+                    if torch.is_tensor(v) and v.is_cuda:
+                        v.record_stream(main)
+            loss = loss_from_features(self.model, feats, batch, self.loss, self.normalization)
         with segment("backward"):
             loss.backward()
         if self.flat and self.nan_guard:
@@ -367,20 +355,12 @@ class Trainer:
             for v in batch.values():
                 if torch.is_tensor(v) and v.is_cuda:
                     v.record_stream(main)
-        k = _reloc_k(self.model)
-        if self.loss == "strong":
-            vol, delta = _positive_volumes(self.model, batch, return_delta=True) if k > 1 else \
-                (_positive_volumes(self.model, batch), None)
-            if "L_pck" in batch:              # PCK of the same volume, summarised per epoch by process_epoch
-                self._pck.append(batch_pck(vol, batch, delta4d=delta, k_size=k))
-            return strong_loss_from_corr(vol, batch).detach()
-        if self.loss == "warp":
-            vol, delta = _positive_volumes(self.model, batch, return_delta=True) if k > 1 else \
-                (_positive_volumes(self.model, batch), None)
-            if "L_pck" in batch and "source_points" in batch:
-                self._pck.append(batch_pck(vol, batch, delta4d=delta, k_size=k))
-            return warp_loss_from_corr(vol, batch).detach()
-        return weak_loss(self.model, batch, self.normalization).detach()
+        spec = LOSSES[self.loss]
+        vol, delta = _batch_volumes(self.model, batch, spec.negatives)
+        if spec.pck_fields is not None and all(k in batch for k in spec.pck_fields):
+            # PCK of the same volume, summarised per epoch by process_epoch
+            self._pck.append(batch_pck(vol, batch, delta4d=delta, k_size=_reloc_k(self.model)))
+        return spec.from_corr(vol, batch, self.normalization).detach()
 
     def _log(self, rec: dict):
         if self.metrics_path:
@@ -436,7 +416,7 @@ class Trainer:
         mean = float(all_reduce_mean(total / max(n, 1), self.ctx))
         if self.ctx.is_main:
             print(f"{mode.capitalize()} set: Average loss: {mean:.4f}", flush=True)
-        if not is_train and self.loss in ("strong", "warp") and self._pck:
+        if not is_train and self._pck:
             # mean over this rank's samples with keypoints, then over ranks
             pck = torch.cat(self._pck).float()
             self._pck = []

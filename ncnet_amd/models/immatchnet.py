@@ -4,6 +4,12 @@ Reference: lib/model.py:19-282.  Module names (``FeatureExtraction.model``,
 ``NeighConsensus.conv.{0,2,4}``) and parameter shapes match the reference so
 ``.pth.tar`` checkpoints load unchanged.
 
+After the backbone there are two entries: ``match_features`` (inference, one
+set of pairs) and ``training_volumes`` (every training loss; positives, plus
+the weak loss's rolled negatives).  Both get their correlation volumes from
+ops/correlation.py ``pair_volumes``, which owns the route choice, and finish
+in ``process_correlation``.
+
 Compute policy (MI355X):
 * the frozen backbone runs in eval mode under ``no_grad``, bf16, channels-last
   (MIOpen); frozen BN is optionally folded into the convs;
@@ -26,8 +32,8 @@ import torch.nn.functional as F
 
 from ..ops import reference as ref
 from ..ops.conv4d import Conv4d
-from ..ops.correlation import (_device_map, correlation, correlation_pool2, correlation_x3, l2norm_pack,
-                               l2norm_pack_f16, l2norm_pack_fp8, l2norm_pack_split, maxpool4d as _maxpool4d)
+from ..ops.correlation import (correlation, fuses_pool, l2norm_pack, l2norm_pack_f16, l2norm_pack_fp8,
+                               l2norm_pack_split, maxpool4d as _maxpool4d, pair_volumes, weak_loss_maps)
 from ..ops import _ext as _ext_mod
 from ..ops.mutual import (mutual_matching, mutual_matching_nc_input as _mm_nc_input,
                           mutual_matching_padded as _mm_padded)
@@ -203,28 +209,6 @@ def _load_reference_checkpoint(path: str):
     ck = load_checkpoint(path)
     ck["state_dict"] = OrderedDict((k.replace("vgg", "model"), v) for k, v in ck["state_dict"].items())
     return ck
-
-
-_MAPS: dict = {}
-
-
-def _pair_maps(b: int, device):
-    """Batch index maps of the positive pairs (a_i, b_i) followed by the rolled
-    negatives (a_{i+1}, b_i) (train.py:137), cached per (b, device)."""
-    key = (b, str(device))
-    m = _MAPS.get(key)
-    if m is None:
-        ar = torch.arange(b, device=device, dtype=torch.int32)
-        m = (torch.cat((ar, torch.roll(ar, -1))), torch.cat((ar, ar)))
-        _MAPS[key] = m
-    return m
-
-
-def _pair_map_lists(b: int):
-    """``_pair_maps`` as host int tuples (the pooled correlation's backward
-    builds its per-image volume lists from them on the host)."""
-    ar = tuple(range(b))
-    return ar + ar[1:] + ar[:1], ar + ar
 
 
 class ImMatchNet(nn.Module):
@@ -405,76 +389,42 @@ class ImMatchNet(nn.Module):
         ``packed_offsets``: the k=2 max-pool offsets as one uint8 volume of 2-bit
         codes (decoded at the matched cells by eval/point_tnf.py) instead of
         four decoded volumes."""
-        (ha, wa), (hb, wb) = hwa, hwb
-        b = (fa[0] if isinstance(fa, tuple) else fa).shape[0]
         k = self.relocalization_k_size
-        if isinstance(fa, tuple):
-            corr4d = correlation_x3(fa, fb).view(b, 1, ha, wa, hb, wb)
-            if k > 1:
-                corr4d, delta = _maxpool4d(corr4d, k)
-        elif k > 1:
-            if k == 2 and ha % 2 == 0 and wa % 2 == 0 and hb % 2 == 0 and wb % 2 == 0:
-                corr4d, delta = correlation_pool2(fa, fb, ha, wa, hb, wb, packed=packed_offsets)
-            else:
-                corr4d = correlation(fa, fb).view(b, 1, ha, wa, hb, wb)
-                corr4d, delta = _maxpool4d(corr4d, k)
-        else:
-            corr4d = correlation(fa, fb).view(b, 1, ha, wa, hb, wb)
+        corr4d, delta = pair_volumes(fa, fb, hwa, hwb, k=k, packed_offsets=packed_offsets)
         corr4d = self.process_correlation(corr4d)
         if k > 1:
             return corr4d, delta
         return corr4d
 
-    def _relocalized_volumes(self, f, hw, b: int, amap, bmap):
-        """Pooled training volumes (``relocalization_k_size`` > 1) of the pairs
-        (source amap[v], target bmap[v]) -- host int tuples, None: pair v = (v, v) -- from ``f`` =
-        extract() of [source; target]: (pooled [V,1,h/k,w/k,h/k,w/k], offsets).
-        k = 2 on even grids with bf16 operands is the fused mapped pool (with its
-        HIP backward when the trunk trains); split (hi, lo) operands pool the
-        bf16x3 volume; any other k, or odd grids, pool the full volume -- frozen
-        trunk only (the unfused pool has no backward)."""
-        h, w = hw
+    def training_volumes(self, f, hw, b: int, negatives: bool, return_delta: bool = False):
+        """The training step after the backbone, for every loss: ``f`` =
+        extract() of the 2B images [source; target] (a tensor, or split (hi, lo)
+        operands) -> the positive volumes [B,1,h,w,h,w], followed with
+        ``negatives`` by the B rolled negatives (``weak_loss_maps``), through
+        MutualMatching / NeighConsensus / MutualMatching.  With
+        ``relocalization_k_size`` k > 1 the volumes are max-pooled k x k x k x k
+        before the NC stack ([V,1,h/k,..]); ``return_delta``: also the pool's
+        offsets (``None`` without pooling), as ``match_features``.  The unfused
+        pool (k != 2 or odd grids) has no backward: frozen trunk only."""
         k = self.relocalization_k_size
-        V = len(amap) if amap is not None else b
-        dev = (f[0] if isinstance(f, tuple) else f).device
-        # device copies for the un-fused routes (None: the identity, the positive pairs)
-        am = _device_map(amap, dev) if amap is not None else None
-        bm = _device_map(bmap, dev) if bmap is not None else None
-        if isinstance(f, tuple):               # split operands: the trunk is frozen (extract)
-            if _nc_ops.x3_dropped("corr"):
-                f = (f[0], torch.zeros_like(f[1]))
-            corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]), am, bm)
-            return _maxpool4d(corr.view(V, 1, h, w, h, w), k)
-        fa, fb = f[:b], f[b:]
-        if k == 2 and h % 2 == 0 and w % 2 == 0:
-            return correlation_pool2(fa, fb, h, w, h, w, amap=amap, bmap=bmap)
-        if torch.is_grad_enabled() and f.requires_grad:
-            raise ValueError(f"relocalization_k_size={k} on a {h} x {w} feature grid has no backward into a "
+        split = isinstance(f, tuple)           # nc_precision / corr_dtype 'fp32': the trunk is frozen (extract)
+        if split and _nc_ops.x3_dropped("corr"):    # precision ablation: bf16 correlation operands
+            f = (f[0], torch.zeros_like(f[1]))
+        fa, fb = ((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:])) if split else (f[:b], f[b:])
+        if k > 1 and not split and not fuses_pool(fa, hw, hw, k) and torch.is_grad_enabled() and f.requires_grad:
+            raise ValueError(f"relocalization_k_size={k} on a {hw[0]} x {hw[1]} feature grid has no backward into a "
                              "trainable trunk: training through the pooled correlation needs k = 2 and even grids")
-        return _maxpool4d(correlation(fa, fb, am, bm).view(V, 1, h, w, h, w), k)
+        amap, bmap = weak_loss_maps(b) if negatives else (None, None)
+        with segment("correlation"):
+            corr, delta = pair_volumes(fa, fb, hw, hw, amap, bmap, k)
+        corr = self.process_correlation(corr)
+        return (corr, delta) if return_delta else corr
 
     def match_volumes_from_features(self, f: torch.Tensor, hw, b: int, return_delta: bool = False):
-        """The positive volumes [B,1,h,w,h,w] alone, from ``f`` = extract() of
-        the 2B images [source; target] (the keypoint-supervised loss: no rolled
-        negatives, so the NC stack runs on half the volumes of a weak step).
-        With ``relocalization_k_size`` k > 1 the volumes are max-pooled k x k x k x k
-        before the NC stack ([B,1,h/k,..]); ``return_delta``: also the pool's
-        offsets (``None`` without pooling), as ``match_features``."""
-        h, w = hw
-        if self.relocalization_k_size > 1:
-            with segment("correlation"):
-                corr, delta = self._relocalized_volumes(f, hw, b, None, None)
-            corr = self.process_correlation(corr)
-            return (corr, delta) if return_delta else corr
-        with segment("correlation"):
-            if isinstance(f, tuple):           # split operands (nc_precision / corr_dtype 'fp32')
-                if _nc_ops.x3_dropped("corr"):
-                    f = (f[0], torch.zeros_like(f[1]))
-                corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]))
-            else:
-                corr = correlation(f[:b], f[b:])
-        corr = self.process_correlation(corr.view(b, 1, h, w, h, w))
-        return (corr, None) if return_delta else corr
+        """The positive volumes alone (the keypoint- and warp-supervised losses:
+        no rolled negatives, so the NC stack runs on half the volumes of a weak
+        step): ``training_volumes`` without negatives."""
+        return self.training_volumes(f, hw, b, False, return_delta)
 
     def weak_loss_volumes(self, src: torch.Tensor, tgt: torch.Tensor) -> torch.Tensor:
         """Positive and rolled-negative volumes [2B,1,h,w,h,w] for the weak loss.
@@ -489,30 +439,7 @@ class ImMatchNet(nn.Module):
         return self.weak_loss_volumes_from_features(f, hw, b)
 
     def weak_loss_volumes_from_features(self, f: torch.Tensor, hw, b: int, return_delta: bool = False):
-        """``weak_loss_volumes`` after the backbone: ``f`` = extract() of the
-        2B images [source; target] (engine/trainer.py TrunkPrefetcher runs it
-        one step ahead on a side stream when the trunk is frozen).  With
-        ``relocalization_k_size`` k > 1 the volumes are max-pooled k x k x k x k
-        before the NC stack; ``return_delta``: also the pool's offsets (``None``
-        without pooling)."""
-        h, w = hw
-        if self.relocalization_k_size > 1:
-            amap, bmap = _pair_map_lists(b)
-            with segment("correlation"):
-                corr, delta = self._relocalized_volumes(f, hw, b, amap, bmap)
-            corr = self.process_correlation(corr)
-            return (corr, delta) if return_delta else corr
-        if return_delta:
-            return self.weak_loss_volumes_from_features(f, hw, b), None
-        if isinstance(f, tuple):               # split operands (nc_precision / corr_dtype 'fp32')
-            if _nc_ops.x3_dropped("corr"):     # precision ablation: bf16 correlation operands
-                f = (f[0], torch.zeros_like(f[1]))
-            amap, bmap = _pair_maps(b, f[0].device)
-            with segment("correlation"):
-                corr = correlation_x3((f[0][:b], f[1][:b]), (f[0][b:], f[1][b:]), amap, bmap)
-            return self.process_correlation(corr.view(2 * b, 1, h, w, h, w))
-        fa, fb = f[:b], f[b:]
-        amap, bmap = _pair_maps(b, f.device)
-        with segment("correlation"):
-            corr = correlation(fa, fb, amap, bmap).view(2 * b, 1, h, w, h, w)
-        return self.process_correlation(corr)
+        """``weak_loss_volumes`` after the backbone (engine/trainer.py
+        TrunkPrefetcher runs that one step ahead on a side stream when the trunk
+        is frozen): ``training_volumes`` with the rolled negatives."""
+        return self.training_volumes(f, hw, b, True, return_delta)

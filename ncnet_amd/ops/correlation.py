@@ -11,6 +11,11 @@
   and packed argmax offsets are written.  It takes the same pair maps, and
   bf16 features that require grad get the HIP backward ``corr_pool2_bwd``
   (``CorrelationPool2Fn``; relocalized training with a trainable trunk).
+* ``pair_volumes``: the one place that chooses among them (and
+  ``correlation_x3`` / ``maxpool4d``) for a set of pairs; the model's inference
+  and training entries both call it.  Pair maps travel as host int sequences
+  (``weak_loss_maps`` builds the weak loss's); ``_device_map`` caches their
+  device copies.
 * IEEE-half inference (``corr_dtype='fp16'``, half_precision models as the
   reference's eval_inloc.py): ``l2norm_pack_f16`` operands on the f16 MFMA.
 * fp32-accurate inference ("bf16x3", ``corr_dtype='fp32'``): the L2-norm
@@ -472,3 +477,38 @@ def maxpool4d(corr4d: torch.Tensor, k_size: int):
         _ext.ext().maxpool4d(x, val, code, k_size)
         return val.unsqueeze(1), decode_offsets(code.unsqueeze(1))
     return ref.maxpool4d(corr4d, k_size)
+
+
+def weak_loss_maps(b: int):
+    """The weak loss's pair maps as host int tuples: the positive pairs
+    (a_i, b_i), then the negatives (a_{i+1}, b_i) -- sources rolled by -1
+    (train.py:137)."""
+    ar = tuple(range(b))
+    return ar + ar[1:] + ar[:1], ar + ar
+
+
+def fuses_pool(fa, hwa, hwb, k: int) -> bool:
+    """Whether ``pair_volumes`` takes the fused pool (``correlation_pool2``):
+    k = 2, all four grid dimensions even, operands not split."""
+    return k == 2 and not isinstance(fa, tuple) and not any(d % 2 for d in (*hwa, *hwb))
+
+
+def pair_volumes(fa, fb, hwa, hwb, amap=None, bmap=None, k: int = 0, packed_offsets: bool = False):
+    """THE route from packed features to correlation volumes: volume v is the
+    pair (fa[amap[v]], fb[bmap[v]]) -- maps as host int sequences (device copies
+    from the ``_device_map`` cache), ``None``: the identity.  Returns (corr4d
+    [V,1,hA',wA',hB',wB'], the pool's offsets or ``None``).  ``fuses_pool``:
+    ``correlation_pool2`` (``packed_offsets`` is its ``packed``); split (hi, lo)
+    operands: ``correlation_x3``, else ``correlation`` -- either followed by
+    ``maxpool4d`` when k > 1 (no backward through that pool).  fp8 / IEEE-half
+    operands stay inference-only inside ``correlation`` / ``correlation_pool2``."""
+    (ha, wa), (hb, wb) = hwa, hwb
+    if fuses_pool(fa, hwa, hwb, k):
+        return correlation_pool2(fa, fb, ha, wa, hb, wb, packed=packed_offsets, amap=amap, bmap=bmap)
+    split = isinstance(fa, tuple)
+    dev = (fa[0] if split else fa).device
+    am = _device_map(amap, dev) if amap is not None else None
+    bm = _device_map(bmap, dev) if bmap is not None else None
+    corr = correlation_x3(fa, fb, am, bm) if split else correlation(fa, fb, am, bm)
+    corr4d = corr.view(corr.shape[0], 1, ha, wa, hb, wb)
+    return maxpool4d(corr4d, k) if k > 1 else (corr4d, None)

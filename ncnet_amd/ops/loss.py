@@ -18,8 +18,12 @@ closed-form backward kernels of csrc/kploss.hip.
 ``warp_loss_from_corr`` is the dense correspondence objective of two warped
 views of one image (``reference.dense_ce``) on the kernels of csrc/densece.hip
 and the same single-pass statistics.
+
+``LOSSES`` (at the end) describes the three as plain data for engine/trainer.py.
 """
 from __future__ import annotations
+
+import collections
 
 import torch
 
@@ -143,7 +147,8 @@ class KeypointCEFn(torch.autograd.Function):
         return gx, None, None, None, None, None
 
 
-_KP_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size")
+# THE keypoint fields of a batch (the loss table below and engine/trainer.py take them from here)
+KEYPOINT_FIELDS = ("source_points", "target_points", "source_im_size", "target_im_size")
 
 
 def strong_loss_from_corr(corr4d: torch.Tensor, batch) -> torch.Tensor:
@@ -152,12 +157,12 @@ def strong_loss_from_corr(corr4d: torch.Tensor, batch) -> torch.Tensor:
     ``target_points`` [B,2,N] and ``*_im_size`` [B,3].  The keypoint tensors are
     used as they are when they already are contiguous fp32 on the volume's
     device (the trainer moves the batch once); nothing is copied per step."""
-    missing = [k for k in _KP_FIELDS if k not in batch]
+    missing = [k for k in KEYPOINT_FIELDS if k not in batch]
     if missing:
         raise KeyError(f"strong loss: the batch has no {missing} (use a dataset with keypoints)")
     if corr4d.dim() != 6 or corr4d.shape[1] != 1:
         raise ValueError(f"strong loss: expected a [B,1,hA,wA,hB,wB] volume, got {tuple(corr4d.shape)}")
-    sp, tp, ssz, tsz = (batch[k] for k in _KP_FIELDS)
+    sp, tp, ssz, tsz = (batch[k] for k in KEYPOINT_FIELDS)
     if _ext.use_hip(corr4d):
         b = corr4d.shape[0]
         ha, wa, hb, wb = corr4d.shape[2:]
@@ -240,3 +245,19 @@ def match_score(corr4d: torch.Tensor, normalization: str | None = "softmax") -> 
         wc = torch.full((V,), 1.0 / (2.0 * V * Cc), device=corr4d.device)
         return SoftmaxMaxScoreFn.apply(corr4d.reshape(V, R, Cc), wr, wc, _NORM[normalization])
     return ref.match_score(corr4d, normalization)
+
+
+# The training losses as data, for engine/trainer.py.  negatives: reads the rolled negative volumes
+# after the positives; fields: the batch tensors a step reads besides the images (kept alive on the
+# main stream); from_corr: (volumes, batch, normalization) -> loss; pck_fields: evaluation also
+# scores PCK when the batch has all of these (None: never).
+LossSpec = collections.namedtuple("LossSpec", "negatives fields from_corr pck_fields")
+
+LOSSES = {
+    "weak": LossSpec(True, (), lambda corr4d, batch, normalization:
+                     weak_loss_from_corr(corr4d, corr4d.shape[0] // 2, normalization), None),
+    "strong": LossSpec(False, KEYPOINT_FIELDS + ("L_pck",), lambda corr4d, batch, normalization:
+                       strong_loss_from_corr(corr4d, batch), ("L_pck",)),
+    "warp": LossSpec(False, ("warp_maps",) + KEYPOINT_FIELDS + ("L_pck",), lambda corr4d, batch, normalization:
+                     warp_loss_from_corr(corr4d, batch), ("L_pck", "source_points")),
+}

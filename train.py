@@ -206,8 +206,19 @@ class _Shard(torch.utils.data.Sampler):
         return self.n // self.ctx.world_size if self.ctx.world_size > 1 else self.n
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def make_augment(args):
+    """The PairAugment of --augment / --loss warp (the ranges of its two views), else None."""
+    if not (args.augment or args.loss == "warp"):
+        return None
+    try:
+        return PairAugment(rot_deg=args.aug_rot_deg, scale=tuple(args.aug_scale), shift=args.aug_shift,
+                           flip=args.aug_flip, gain=tuple(args.aug_gain), bias=args.aug_bias)
+    except ValueError as e:
+        raise SystemExit(f"--{'augment' if args.augment else 'loss warp'}: {e}")
+
+
+def validate_args(args):
+    """Reject flag combinations before anything is built (SystemExit)."""
     strong = args.loss == "strong"
     warp = args.loss == "warp"
     if warp and args.cpu_resize:
@@ -233,13 +244,141 @@ def main(argv=None):
         if args.fe_finetune_params > 0 and k_reloc != 2:
             raise SystemExit("--fe_finetune_params > 0 trains through the pooled correlation, whose backward exists "
                              "for --relocalization_k_size 2 (even feature grids) only")
-    augment = None
-    if args.augment or warp:                       # --loss warp: the ranges of the two views
-        try:
-            augment = PairAugment(rot_deg=args.aug_rot_deg, scale=tuple(args.aug_scale), shift=args.aug_shift,
-                                  flip=args.aug_flip, gain=tuple(args.aug_gain), bias=args.aug_bias)
-        except ValueError as e:
-            raise SystemExit(f"--{'augment' if args.augment else 'loss warp'}: {e}")
+    make_augment(args)
+
+
+def build_data(args, ctx, model):
+    """The per-loss data choices, made once: ``(train_loader, test_loader, tr_sampler, te_sampler,
+    to_device, aug_rng, val_rng)`` -- the Trainer's ``batch_to_device`` hook and the generators of
+    the training augmentation / --loss warp's validation views (None when unused; seeded by main())."""
+    size = (args.image_size, args.image_size)
+    n_test = max(2 * args.batch_size, args.synthetic // 8)
+    augment = make_augment(args)
+    aug_rng = torch.Generator() if augment is not None else None
+    val_rng = None
+    uint8_input = args.gpu_input or args.augment       # asked for: on any device (CPU: the torch fallback)
+    if args.loss == "warp":
+        if args.synthetic:
+            train_set = SyntheticImageDataset(args.synthetic, size, seed=1)
+            test_set = SyntheticImageDataset(n_test, size, seed=2)
+        else:
+            root, tr_names, va_names = warp_image_sets(args)
+            train_set, test_set = SingleImageDataset(root, tr_names), SingleImageDataset(root, va_names)
+        collate = collate_uint8_images
+        val_rng = torch.Generator()      # re-seeded before every validation epoch: same views each time
+        # validation batches also carry the 25 x 25 grid points, for PCK@0.1 of the same volume
+        to_device = lambda batch: gpu_view_batch(  # noqa: E731
+            batch, ctx.device, size[0], size[1], augment, aug_rng if model.training else val_rng,
+            with_points=not model.training)
+    else:
+        strong = args.loss == "strong"
+        # keypoint datasets yield float images unless the uint8 path is asked for
+        gpu_resize = uint8_input or (not strong and ctx.device.type == "cuda" and not args.cpu_resize)
+        if args.synthetic and strong:
+            train_set = SyntheticCorrespondenceDataset(args.synthetic, args.image_size, seed=1)
+            test_set = SyntheticCorrespondenceDataset(n_test, args.image_size, seed=2)
+        elif args.synthetic:
+            train_set = SyntheticPairDataset(args.synthetic, size, seed=1)
+            test_set = SyntheticPairDataset(n_test, size, seed=2)
+        else:
+            kw = dict(output_size=size, transform=NormalizeImageDict(["source_image", "target_image"]),
+                      gpu_resize=gpu_resize)
+            if strong:
+                train_set = PFPascalDataset(args.train_pairs_csv, args.dataset_image_path, **kw)
+                test_set = PFPascalDataset(args.val_pairs_csv, args.dataset_image_path, **kw)
+            else:
+                train_set = ImagePairDataset(args.dataset_csv_path, "train_pairs.csv", args.dataset_image_path, **kw)
+                test_set = ImagePairDataset(args.dataset_csv_path, "val_pairs.csv", args.dataset_image_path, **kw)
+        collate = to_device = None
+        if gpu_resize and not args.synthetic:
+            collate = collate_uint8_pairs
+            # training batches only (the Trainer sets model.training before it touches a loader): validation
+            # keeps the plain resize and its points, so its loss and PCK compare with an un-augmented run
+            to_device = lambda batch: gpu_pair_batch(  # noqa: E731
+                batch, ctx.device, size[0], size[1], augment=augment if model.training else None, generator=aug_rng)
+    tr_sampler = _Shard(len(train_set), ctx, True, args.seed)
+    te_sampler = _Shard(len(test_set), ctx, True, args.seed + 7)
+    pin = ctx.device.type == "cuda"
+    nw = args.num_workers
+    if nw < 0:
+        nw = min(8, max(1, (os.cpu_count() or 2) // max(1, ctx.world_size) - 1)) if pin else 0
+    lkw = dict(batch_size=args.batch_size, num_workers=nw, pin_memory=pin, drop_last=True, collate_fn=collate,
+               persistent_workers=nw > 0, prefetch_factor=4 if nw > 0 else None)
+    train_loader = DataLoader(train_set, sampler=tr_sampler, **lkw)
+    test_loader = DataLoader(test_set, sampler=te_sampler, **lkw)
+    return train_loader, test_loader, tr_sampler, te_sampler, to_device, aug_rng, val_rng
+
+
+def run_max_steps(args, ctx, model, trainer, train_loader, timer):
+    """The bounded --max_steps run (smoke / profiling): no validation, no checkpoint."""
+    model.train()
+    prof = None
+    if args.profile and ctx.is_main:
+        acts = [torch.profiler.ProfilerActivity.CPU]
+        if ctx.device.type == "cuda":
+            acts.append(torch.profiler.ProfilerActivity.CUDA)
+        prof = torch.profiler.profile(activities=acts)
+        prof.__enter__()
+    t0 = time.perf_counter()
+    t_warm, warm = None, min(10, max(0, args.max_steps - 1))
+    steps = 0
+
+    def batches():
+        while True:
+            for b in train_loader:
+                yield b
+    it = batches()
+    steplog = AsyncLossLog(ctx.device, sync=args.sync_log)
+
+    def show(recs):
+        for r in recs:
+            msg = f"step {r['step']} loss {r['loss']:.6f}"
+            if "segments_ms" in r:
+                msg += " " + " ".join(f"{k}={v:.2f}ms" for k, v in r["segments_ms"].items())
+            print(msg, flush=True)
+    nxt = trainer.to_device(next(it))
+    while steps < args.max_steps:
+        batch = nxt
+        # one batch of lookahead, as Trainer.process_epoch: its backbone overlaps this step
+        nxt = trainer.to_device(next(it)) if steps + 1 < args.max_steps else None
+        loss = trainer.train_step(batch, nxt)
+        steps += 1
+        if steps == warm:
+            if ctx.device.type == "cuda":
+                torch.cuda.synchronize()
+            t_warm = time.perf_counter()
+        if ctx.is_main and (steps % max(1, args.log_interval) == 0):
+            meta = {"step": steps}
+            if timer is not None:
+                meta["segments_ms"] = timer.collect()
+            show(steplog.push(loss, meta))
+        elif ctx.is_main:
+            show(steplog.poll())
+    if ctx.is_main:
+        show(steplog.drain())
+    if ctx.device.type == "cuda":
+        torch.cuda.synchronize()
+    if prof is not None:
+        prof.__exit__(None, None, None)
+        os.makedirs(args.profile, exist_ok=True)
+        sort = "cuda_time_total" if ctx.device.type == "cuda" else "cpu_time_total"
+        with open(os.path.join(args.profile, "train_profile.txt"), "w") as f:
+            f.write(prof.key_averages().table(sort_by=sort, row_limit=60))
+        prof.export_chrome_trace(os.path.join(args.profile, "train_trace.json"))
+    if ctx.is_main:
+        t1 = time.perf_counter()
+        dt = t1 - t0
+        msg = f"{steps} steps in {dt:.2f}s ({steps * args.batch_size * ctx.world_size / dt:.1f} pairs/s)"
+        if t_warm is not None and steps > warm:
+            # steady state: excludes DataLoader worker start-up and the first (graph-capturing) steps
+            msg += (f"; steady state after {warm} steps: "
+                    f"{(steps - warm) * args.batch_size * ctx.world_size / (t1 - t_warm):.1f} pairs/s")
+        print(msg)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    validate_args(args)
     ctx = init_distributed()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -269,65 +408,7 @@ def main(argv=None):
             print(f"{i + 1}: {tuple(p.shape)}")
     optimizer = make_adam(params, args.lr)
 
-    size = (args.image_size, args.image_size)
-    uint8_input = args.gpu_input or args.augment       # asked for: on any device (CPU: the torch fallback)
-    gpu_resize = (ctx.device.type == "cuda" and not args.cpu_resize) or uint8_input
-    if warp:
-        gpu_resize = True
-        if args.synthetic:
-            train_set = SyntheticImageDataset(args.synthetic, size, seed=1)
-            test_set = SyntheticImageDataset(max(2 * args.batch_size, args.synthetic // 8), size, seed=2)
-        else:
-            root, tr_names, va_names = warp_image_sets(args)
-            train_set, test_set = SingleImageDataset(root, tr_names), SingleImageDataset(root, va_names)
-    elif strong:
-        # keypoint datasets yield float images unless the uint8 path is asked for
-        gpu_resize = uint8_input
-        if args.synthetic:
-            train_set = SyntheticCorrespondenceDataset(args.synthetic, args.image_size, seed=1)
-            test_set = SyntheticCorrespondenceDataset(max(2 * args.batch_size, args.synthetic // 8), args.image_size,
-                                                      seed=2)
-        else:
-            norm = NormalizeImageDict(["source_image", "target_image"])
-            train_set = PFPascalDataset(args.train_pairs_csv, args.dataset_image_path, output_size=size,
-                                        transform=norm, gpu_resize=gpu_resize)
-            test_set = PFPascalDataset(args.val_pairs_csv, args.dataset_image_path, output_size=size, transform=norm,
-                                       gpu_resize=gpu_resize)
-    elif args.synthetic:
-        train_set = SyntheticPairDataset(args.synthetic, size, seed=1)
-        test_set = SyntheticPairDataset(max(2 * args.batch_size, args.synthetic // 8), size, seed=2)
-    else:
-        norm = NormalizeImageDict(["source_image", "target_image"])
-        train_set = ImagePairDataset(args.dataset_csv_path, "train_pairs.csv", args.dataset_image_path,
-                                     output_size=size, transform=norm, gpu_resize=gpu_resize)
-        test_set = ImagePairDataset(args.dataset_csv_path, "val_pairs.csv", args.dataset_image_path,
-                                    output_size=size, transform=norm, gpu_resize=gpu_resize)
-    tr_sampler = _Shard(len(train_set), ctx, True, args.seed)
-    te_sampler = _Shard(len(test_set), ctx, True, args.seed + 7)
-    pin = ctx.device.type == "cuda"
-    nw = args.num_workers
-    if nw < 0:
-        nw = min(8, max(1, (os.cpu_count() or 2) // max(1, ctx.world_size) - 1)) if pin else 0
-    lkw = dict(batch_size=args.batch_size, num_workers=nw, pin_memory=pin, drop_last=True,
-               collate_fn=collate_uint8_images if warp else
-               collate_uint8_pairs if (gpu_resize and not args.synthetic) else None,
-               persistent_workers=nw > 0, prefetch_factor=4 if nw > 0 else None)
-    train_loader = DataLoader(train_set, sampler=tr_sampler, **lkw)
-    test_loader = DataLoader(test_set, sampler=te_sampler, **lkw)
-    aug_rng = torch.Generator() if augment is not None else None     # seeded below, once the first epoch is known
-    val_rng = torch.Generator() if warp else None    # re-seeded before every validation epoch: same views each time
-    if warp:
-        # validation batches also carry the 25 x 25 grid points, for PCK@0.1 of the same volume
-        trainer_to_device = lambda batch: gpu_view_batch(  # noqa: E731
-            batch, ctx.device, size[0], size[1], augment, aug_rng if model.training else val_rng,
-            with_points=not model.training)
-    elif gpu_resize and not args.synthetic:
-        # training batches only (the Trainer sets model.training before it touches a loader): validation
-        # keeps the plain resize and its points, so its loss and PCK compare with an un-augmented run
-        trainer_to_device = lambda batch: gpu_pair_batch(  # noqa: E731
-            batch, ctx.device, size[0], size[1], augment=augment if model.training else None, generator=aug_rng)
-    else:
-        trainer_to_device = None
+    train_loader, test_loader, tr_sampler, te_sampler, to_device, aug_rng, val_rng = build_data(args, ctx, model)
 
     checkpoint_name = os.path.join(args.result_model_dir,
                                    datetime.datetime.now().strftime("%Y-%m-%d_%H:%M") + "_" + args.result_model_fn +
@@ -358,76 +439,20 @@ def main(argv=None):
     timer = SegmentTimer(device=ctx.device) if args.segment_timing else None
     set_active(timer)
     trainer = Trainer(model, optimizer, ctx, metrics_path=args.metrics or None, loss=args.loss)
-    trainer.batch_to_device = trainer_to_device
+    trainer.batch_to_device = to_device
     if args.max_steps:
-        # bounded run (smoke / profiling)
-        model.train()
-        prof = None
-        if args.profile and ctx.is_main:
-            acts = [torch.profiler.ProfilerActivity.CPU]
-            if ctx.device.type == "cuda":
-                acts.append(torch.profiler.ProfilerActivity.CUDA)
-            prof = torch.profiler.profile(activities=acts)
-            prof.__enter__()
-        t0 = time.perf_counter()
-        t_warm, warm = None, min(10, max(0, args.max_steps - 1))
-        steps = 0
+        run_max_steps(args, ctx, model, trainer, train_loader, timer)
+    else:
+        run_epochs(args, ctx, model, optimizer, trainer, (train_loader, test_loader, tr_sampler), val_rng,
+                   (start_epoch, train_loss, test_loss, best_test_loss, checkpoint_name))
+    set_active(None)
+    destroy(ctx)
 
-        def batches():
-            while True:
-                for b in train_loader:
-                    yield b
-        it = batches()
-        steplog = AsyncLossLog(ctx.device, sync=args.sync_log)
 
-        def show(recs):
-            for r in recs:
-                msg = f"step {r['step']} loss {r['loss']:.6f}"
-                if "segments_ms" in r:
-                    msg += " " + " ".join(f"{k}={v:.2f}ms" for k, v in r["segments_ms"].items())
-                print(msg, flush=True)
-        nxt = trainer.to_device(next(it))
-        while steps < args.max_steps:
-            batch = nxt
-            # one batch of lookahead, as Trainer.process_epoch: its backbone overlaps this step
-            nxt = trainer.to_device(next(it)) if steps + 1 < args.max_steps else None
-            loss = trainer.train_step(batch, nxt)
-            steps += 1
-            if steps == warm:
-                if ctx.device.type == "cuda":
-                    torch.cuda.synchronize()
-                t_warm = time.perf_counter()
-            if ctx.is_main and (steps % max(1, args.log_interval) == 0):
-                meta = {"step": steps}
-                if timer is not None:
-                    meta["segments_ms"] = timer.collect()
-                show(steplog.push(loss, meta))
-            elif ctx.is_main:
-                show(steplog.poll())
-        if ctx.is_main:
-            show(steplog.drain())
-        if ctx.device.type == "cuda":
-            torch.cuda.synchronize()
-        if prof is not None:
-            prof.__exit__(None, None, None)
-            os.makedirs(args.profile, exist_ok=True)
-            sort = "cuda_time_total" if ctx.device.type == "cuda" else "cpu_time_total"
-            with open(os.path.join(args.profile, "train_profile.txt"), "w") as f:
-                f.write(prof.key_averages().table(sort_by=sort, row_limit=60))
-            prof.export_chrome_trace(os.path.join(args.profile, "train_trace.json"))
-        if ctx.is_main:
-            t1 = time.perf_counter()
-            dt = t1 - t0
-            msg = f"{steps} steps in {dt:.2f}s ({steps * args.batch_size * ctx.world_size / dt:.1f} pairs/s)"
-            if t_warm is not None and steps > warm:
-                # steady state: excludes DataLoader worker start-up and the first (graph-capturing) steps
-                msg += (f"; steady state after {warm} steps: "
-                        f"{(steps - warm) * args.batch_size * ctx.world_size / (t1 - t_warm):.1f} pairs/s")
-            print(msg)
-        set_active(None)
-        destroy(ctx)
-        return
-
+def run_epochs(args, ctx, model, optimizer, trainer, data, val_rng, state):
+    """Train, validate, checkpoint.  ``state``: (first epoch, loss histories, best loss, checkpoint name)."""
+    train_loader, test_loader, tr_sampler = data
+    start_epoch, train_loss, test_loss, best_test_loss, checkpoint_name = state
     if ctx.is_main:
         print("Starting training...")
     for epoch in range(start_epoch, args.num_epochs + 1):
@@ -446,8 +471,6 @@ def main(argv=None):
         barrier(ctx)
     if ctx.is_main:
         print("Done!")
-    set_active(None)
-    destroy(ctx)
 
 
 if __name__ == "__main__":
